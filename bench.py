@@ -1,15 +1,19 @@
 """EncDiff training benchmark on MI355X (driver contract: one JSON line on rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (data-parallel, RCCL)
 
 Metric (BASELINE.json): training imgs/sec on Shapes3D 64x64 (VQ-f4, 16x16 latent),
 configs[1]: batch 128 per GPU, bf16 HIP path.  A step = one full LatentDiffusion
 training step: frozen VQ encode + Encoder4 + q_sample + UNet fwd/bwd + L1 + AdamW +
 EMA (+ RCCL gradient all-reduce when N > 1).  Inputs: synthetic images resident in HBM
-(no dataset / checkpoint is available offline).  Also reported: DDIM sampling steps/s,
-the roofline of the dominant kernel measured live with HIP events, and the CPU
-oracle (the repo's restatement of the reference) timed on this host's cores.
+(no dataset / checkpoint is available offline).
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --dump-outputs DIR
+also writes what the last timed step computed as DIR/<name>.npy (`dump_outputs`).  --full adds the
+measurements that take runs of their own: DDIM sampling steps/s, the roofline of the dominant
+kernel measured live with HIP events, the DP exchange timing, the eager reference-API step, and the
+CPU oracle (the repo's restatement of the reference) timed on this host's cores.
 """
 from __future__ import annotations
 
@@ -39,6 +43,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (float32, seeded samples of the arenas)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the GEMM roofline, DP exchange timing, DDIM rates, the eager reference-API "
+                         "step and the CPU baseline (the --skip-* / --ddim-* options select among these)")
     ap.add_argument("--ddim-steps", type=int, default=200)
     ap.add_argument("--ddim-batch", type=int, default=8)
     ap.add_argument("--skip-ddim", action="store_true")
@@ -383,6 +392,39 @@ def cpu_baseline(warmup=3, steps=50, ddim_steps=50, probe_steps=4):
                                    "threads": best}}
 
 
+DUMP_SAMPLE = 2 * 1024 * 1024  # elements kept of each arena-sized array (8 MB as float32)
+
+
+def dump_outputs(tr, outdir, rank=0):
+    """What the timed path left after its last step, as <outdir>/<name>.npy (float32; rank r > 0
+    writes <name>.rank<r>.npy): `loss` (loss_simple, loss_vlb), `eps` (the denoiser output of
+    the last batch), and of the flat arenas the step updates -- `grad` (the step's gradients),
+    `params` (fp32 master weights after AdamW), `ema` -- of each the same DUMP_SAMPLE elements
+    in every run (arena positions drawn from a fixed seed), about 25 MB in all."""
+    import numpy as np
+    torch.cuda.synchronize()
+    os.makedirs(outdir, exist_ok=True)
+    sfx = "" if rank == 0 else f".rank{rank}"
+
+    def save(name, t):
+        np.save(os.path.join(outdir, f"{name}{sfx}.npy"), t.detach().float().cpu().contiguous().numpy())
+
+    def sample(flat):
+        n = flat.numel()
+        if n <= DUMP_SAMPLE:
+            return flat
+        idx = np.sort(np.random.default_rng(20240229).integers(0, n, DUMP_SAMPLE))
+        return flat[torch.from_numpy(idx).to(flat.device)]
+
+    a = tr.arena
+    save("loss", tr.loss_buf[:2])
+    save("eps", tr.eps())
+    save("grad", sample(a.grad))
+    save("params", sample(a.master))
+    if a.ema is not None:
+        save("ema", sample(a.ema))
+
+
 def main():
     args = parse()
     rank, world = setup_dist(args)
@@ -402,8 +444,10 @@ def main():
     dt = time_steps(tr, args.steps, events=ev)
     torch.cuda._sleep(1000)
     local_ms = ev[0].elapsed_time(ev[1]) / args.steps  # this rank's GPU time per step
+    if args.dump_outputs:  # the state the last timed step left, before any further step moves it
+        dump_outputs(tr, args.dump_outputs, rank)
     dp_info = None
-    if tr.dp:  # exchange timing on extra steps (the timed ones carry no extra events)
+    if tr.dp and args.full:  # exchange timing on extra steps (the timed ones carry no extra events)
         tr.dp_timing = True
         for _ in range(min(10, args.steps)):
             tr.step()
@@ -427,9 +471,11 @@ def main():
     value = imgs / dt
     loss = tr.loss()
     extra = {}
-    roof = kernel_roofline(tr, config=args.config, batch=args.batch)  # every rank (its recording step runs the DP exchange)
+    # every rank (its recording step runs the DP exchange)
+    roof = kernel_roofline(tr, config=args.config, batch=args.batch) if args.full else None
     if rank == 0:
-        extra["roofline"] = roof
+        if roof is not None:
+            extra["roofline"] = roof
         if dp_info is not None:
             extra["dp"] = dp_info
         if dist_info is not None:
@@ -441,7 +487,7 @@ def main():
                                       "peak": PEAK_BF16_TFLOPS,
                                       "frac": f_step * args.steps / dt / 1e12 / PEAK_BF16_TFLOPS,
                                       "flops_per_img": 3 * F_UNET_FWD_PER_IMG}
-        if not args.skip_ddim:
+        if args.full and not args.skip_ddim:
             # DDIM steps/s at (B=8, S=200, eta=0) and (B=128, S=200, eta=1)
             extra["ddim_steps_per_sec"] = {"value": ddim_rate(ldm, args.ddim_batch, args.ddim_steps),
                                            "batch": args.ddim_batch, "S": args.ddim_steps, "eta": 0.0}
@@ -449,11 +495,11 @@ def main():
                                                 "batch": 128, "S": args.ddim_steps, "eta": 1.0}
             if args.config == "shapes3d":
                 extra["ddim_log_images_s"] = log_images_time(ldm)
-        if not args.skip_ref_api and world == 1:
+        if args.full and not args.skip_ref_api and world == 1:
             r = ref_api_time(args.config, args.batch)
             extra["ref_api_ms_per_step"] = r["ms_per_step"]
             extra["ref_api"] = r
-        if not args.skip_cpu and world == 1 and args.config == "shapes3d":  # CPU baseline: N=1, configs[1]
+        if args.full and not args.skip_cpu and world == 1 and args.config == "shapes3d":  # CPU baseline: N=1, configs[1]
             extra["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         out = {"metric": metric, "value": value, "unit": "imgs/s",

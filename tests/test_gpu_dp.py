@@ -71,7 +71,7 @@ def test_dp_two_ranks_equal_single_process_definition(tmp_path):
 
 @pytest.mark.parametrize("wire", ["fp32", "bf16"])
 def test_dp_exchange_over_rccl_one_rank(tmp_path, wire):
-    """The RCCL side of the exchange on a one-GPU box: bench.py under torch.distributed.run with
+    """The RCCL side of the exchange on a one-GPU box: bench.py --full under torch.distributed.run with
     ONE rank, backend "nccl" (= RCCL) and ENCDIFF_DP_FORCE=1, so the step runs the full DP path --
     split backward, the four captured graphs, the bucketed all-reduces (ReduceOp.AVG over the
     RCCL communicator) on the side stream with the host-issued waits.  A mean over one rank is the
@@ -94,13 +94,16 @@ def test_dp_exchange_over_rccl_one_rank(tmp_path, wire):
         return json.loads([ln for ln in out.splitlines() if ln.startswith('{"metric"')][-1])
 
     dp = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
-              "--master-addr", "127.0.0.1", "--master-port", "29631" if wire == "fp32" else "29633", *args],
+              "--master-addr", "127.0.0.1", "--master-port", "29631" if wire == "fp32" else "29633", *args, "--full"],
              str(tmp_path / "rccl.log"), env)
     plain_env = dict(os.environ)
     plain_env.pop("ENCDIFF_DP_FORCE", None)
     # the DP run takes min(10, steps) extra exchange-timing steps before it reads the loss
     plain_args = [a if a != "4" else "8" for a in args]
     plain = run([sys.executable, *plain_args], str(tmp_path / "plain.log"), plain_env)
+    # a run without --full times its steps and nothing else
+    assert not {"roofline", "dp", "ref_api", "cpu_baseline", "ddim_steps_per_sec"} & set(plain), sorted(plain)
+    assert plain["steps"] == 8 and abs(plain["value"] - 32 * 1000.0 / plain["ms_per_step"]) / plain["value"] < 1e-6
     print("RCCL one-rank exchange:", dp.get("dp"), "loss", dp["loss_simple_last"], "plain", plain["loss_simple_last"])
     assert dp.get("dp") is not None and dp["dp"]["split_backward"], dp.get("dp")
     # every coarse bucket's all-reduce was issued (timed on the exchange stream)

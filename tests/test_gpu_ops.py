@@ -605,6 +605,13 @@ def test_wgrad_group(O):
     host, devb = arr[0][:2]
     O.check(O.lib.encdiff_wgrad_group_launch(O.C.addressof(host), devb.data_ptr(), O._s()), "group")
     torch.cuda.synchronize()
+    for i, ((dw, _, _, db, _, _), (f_dw, f_db)) in enumerate(zip(cases, first)):
+        if not (torch.equal(dw, f_dw) and torch.equal(db, f_db)):
+            bad = (dw != f_dw).nonzero()
+            print(f"case {i} {tuple(dw.shape)}: {bad.shape[0]} dW elements differ, first {bad[:4].tolist()} last "
+                  f"{bad[-4:].tolist()}, max |d| {(dw - f_dw).abs().max().item():.3e}, vs ref first "
+                  f"{rel(f_dw - cases[i][1], cases[i][2]):.3e} second {rel(dw - cases[i][1], cases[i][2]):.3e}; "
+                  f"db differ {(db != f_db).sum().item()}")
     for (dw, _, _, db, _, _), (f_dw, f_db) in zip(cases, first):
         assert torch.equal(dw, f_dw) and torch.equal(db, f_db)
 

@@ -62,8 +62,9 @@ def build():
         for sym in syms:
             f.write(f"__attribute__((aligned(4096))) char {sym}[4096] = {{0}};\n")
     subprocess.run(["gcc", "-c", "-fPIC", stub_c, "-o", stub_o], check=True)
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-fsanitize=address", "-shared-libsan",
-                        "-o", LIB + ".tmp", *objs, stub_o], capture_output=True, text=True)
+    # host objects only: the link instruments nothing for the device (-fno-gpu-sanitize)
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-fsanitize=address", "-fno-gpu-sanitize",
+                        "-shared-libsan", "-o", LIB + ".tmp", *objs, stub_o], capture_output=True, text=True)
     if r.returncode:
         raise RuntimeError(f"asan link failed:\n{r.stderr}")
     os.replace(LIB + ".tmp", LIB)
