@@ -185,6 +185,13 @@ class PackJob(C.Structure):
                 ("kind", C.c_int), ("cin", C.c_int)]
 
 
+class VqArgs(C.Structure):
+    _fields_ = [("batch", C.c_int), ("hw", C.c_int), ("e_dim", C.c_int), ("n_e", C.c_int),
+                ("z_ch", C.c_int), ("dis_dim", C.c_int), ("quantize", C.c_int), ("pad_", C.c_int),
+                ("z", vp), ("codebook", vp), ("table", vp), ("wq", vp), ("wd", vp), ("bias", vp), ("repr", vp),
+                ("idx", vp), ("zq", vp), ("rows", vp), ("ld_rows", C.c_long)]
+
+
 _PROTOS = {
     "encdiff_gemm": [C.POINTER(GemmArgs), vp],
     "encdiff_gemm_pair": [C.POINTER(GemmArgs), C.POINTER(GemmArgs), vp],
@@ -244,6 +251,7 @@ _PROTOS = {
     "encdiff_resconv_fwd": [C.POINTER(ResConvArgs), vp],
     "encdiff_resconv_query": [C.POINTER(ResConvArgs), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "encdiff_step_prologue": [C.POINTER(StepPrologueArgs), vp],
+    "encdiff_vq_lookup": [C.POINTER(VqArgs), vp],
     "encdiff_version": [],
 }
 

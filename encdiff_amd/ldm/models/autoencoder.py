@@ -89,13 +89,18 @@ class VQModelInterface(VQModel):
         super().__init__(embed_dim=embed_dim, *args, **kwargs)
         self.embed_dim = embed_dim
         self._hip_encoder = None
+        self._hip_decoder = None
 
-    def enable_hip(self):
+    def enable_hip(self, decoder=False):
         """Route encode() through the HIP executor of the frozen encoder
         (encdiff_amd/vq.py).  Called by LatentDiffusion when it sets
-        up HIP training; the module itself stays the reference's (state_dict, decode)."""
-        from encdiff_amd.vq import VQEncoderExecutor
+        up HIP training; the module itself stays the reference's (state_dict, decode).
+        decoder=True also routes decode() (quantizer lookup, post_quant_conv, Decoder) through
+        its HIP executor; without it decode() stays the torch code below."""
+        from encdiff_amd.vq import VQDecoderExecutor, VQEncoderExecutor
         self._hip_encoder = VQEncoderExecutor(self)
+        if decoder:
+            self._hip_decoder = VQDecoderExecutor(self)
         return self
 
     def encode(self, x):
@@ -104,6 +109,9 @@ class VQModelInterface(VQModel):
         return self.quant_conv(self.encoder(x))
 
     def decode(self, h, force_not_quantize=False, disentangled_repr=None):
+        if self._hip_decoder is not None:
+            return self._hip_decoder.decode(h, force_not_quantize=force_not_quantize,
+                                            disentangled_repr=disentangled_repr)
         quant = h if force_not_quantize else self.quantize(h)[0]
         if self.use_disentangled_concat:
             B, _, H, W = quant.shape

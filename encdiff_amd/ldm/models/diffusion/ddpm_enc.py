@@ -521,8 +521,13 @@ class LatentDiffusion(DDPM):
                 arena.alias(n[len("model.diffusion_model."):], n)
         unet.bind_arena(arena)
         fs = self.first_stage_model
-        if hasattr(fs, "enable_hip") and getattr(fs, "_hip_encoder", None) is None:
-            fs.enable_hip()                              # frozen VQ encoder on HIP (§8(f) row 2)
+        # ENCDIFF_VQ_DECODE_HIP=1: decode_first_stage on the HIP decoder executor too (opt-in)
+        vq_dec = os.environ.get("ENCDIFF_VQ_DECODE_HIP", "0") == "1"
+        if hasattr(fs, "enable_hip"):
+            if vq_dec and getattr(fs, "_hip_decoder", None) is None:
+                fs.enable_hip(decoder=True)
+            elif getattr(fs, "_hip_encoder", None) is None:
+                fs.enable_hip()                          # frozen VQ encoder on HIP (§8(f) row 2)
         cs = self.cond_stage_model
         if self.cond_stage_trainable and cs is not None and hasattr(cs, "bind_arena"):
             cs.bind_arena(arena, "cond_stage_model.")   # Encoder4.warp on HIP (§8(f) row 2)

@@ -1246,6 +1246,58 @@ def pack_conv_pad8(w):
     return out.reshape(co, 72).to(BF16).contiguous()
 
 
+VQ_MAX_DIM, VQ_MAX_CODES = 8, 8192  # vq.hip
+
+
+def vq_supported(n_e: int, e_dim: int) -> bool:
+    return 1 <= e_dim <= VQ_MAX_DIM and 1 <= n_e <= VQ_MAX_CODES
+
+
+def _f32c(t, shape, what):
+    assert t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \
+        f"{what}: contiguous fp32 {tuple(shape)} expected, got {t.dtype} {tuple(t.shape)}"
+    return t
+
+
+def vq_lookup(z, codebook=None, *, quantize=True, idx=None, zq=None, rows=None, table=None, wq=None, wd=None,
+              bias=None, repr=None):
+    """VQ decode head on z fp32 NCHW [B][e_dim][H][W], one launch (EncdiffVqArgs).  quantize: the
+    nearest entry of codebook [n_e][e_dim] per pixel (direct fp32 distance, ties to the lowest
+    index) into idx int32 [B*H*W] and zq (as z), both optional.  rows bf16 [B*H*W][8] receives
+    post_quant_conv(cat(zq or z, repr)): table[idx] (quantize; table = pack of codebook and the
+    conv) or wq z, + wd repr[b] + bias, channels z_ch..7 zero; repr None means zeros."""
+    B, e_dim, H, W = z.shape
+    _f32c(z, z.shape, "z")
+    a = L.VqArgs(batch=B, hw=H * W, e_dim=e_dim, quantize=int(bool(quantize)), z=_p(z))
+    if quantize:
+        a.n_e = codebook.shape[0]
+        a.codebook = _p(_f32c(codebook, (a.n_e, e_dim), "codebook"))
+        if idx is not None:
+            assert idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == B * H * W
+            a.idx = _p(idx)
+        if zq is not None:
+            a.zq = _p(_f32c(zq, z.shape, "zq"))
+    else:
+        assert idx is None and zq is None, "quantize=False looks nothing up"
+    if rows is not None:
+        assert rows.dtype == BF16 and rows.shape == (B * H * W, 8)
+        a.z_ch = bias.shape[0]
+        a.bias = _p(_f32c(bias, (a.z_ch,), "bias"))
+        if quantize:
+            a.table = _p(_f32c(table, (a.n_e, a.z_ch), "table"))
+        else:
+            a.wq = _p(_f32c(wq, (a.z_ch, e_dim), "wq"))
+        if wd is not None and wd.shape[1] > 0:
+            a.dis_dim = wd.shape[1]
+            a.wd = _p(_f32c(wd, (a.z_ch, a.dis_dim), "wd"))
+            if repr is not None:
+                a.repr = _p(_f32c(repr, (B, a.dis_dim), "repr"))
+        else:
+            assert repr is None, "a representation needs the disentangled slice of post_quant_conv"
+        a.rows, a.ld_rows = _p(rows), _ld(rows)
+    check(lib.encdiff_vq_lookup(C.byref(a), _s()), "encdiff_vq_lookup")
+
+
 def small_conv_out_bwd(x, g: Geom, weight, dy_nchw, dx, dweight, dbias):
     cout, cin = weight.shape[0], weight.shape[1]
     a = L.SmallConvArgs(batch=g.batch, h=g.h, w=g.w, cin=cin, cout=cout, x=_p(x), ldx=_ld(x), x_f32=0,

@@ -853,6 +853,34 @@ typedef struct EncdiffStepPrologueArgs {
 
 int encdiff_step_prologue(const EncdiffStepPrologueArgs* args, void* stream);
 
+/* ---------------------------------------------------------------- VQ decode head
+ * VQModelInterface.decode up to the decoder's conv_in (autoencoder.py:328-369), one launch:
+ * per latent pixel the nearest codebook entry idx = argmin_j sum_c (z_c - E_jc)^2 (evaluated
+ * directly in fp32; ties go to the lowest index), the quantised latent zq = E[idx], and the
+ * decoder's input rows = post_quant_conv(cat(zq, s_b)) as channel-padded bf16 rows (the layout
+ * of encdiff_nchw_to_rows with cpad 8).  The 1x1 conv is linear, so rows = T[idx] + Wd s_b + b
+ * with T = E Wpq[:, :e_dim]^T [n_e][z_ch] composed by the caller.  quantize == 0
+ * (force_not_quantize / predict_cids): rows = Wq z + Wd s_b + b with Wq = Wpq[:, :e_dim];
+ * idx / zq must be NULL.  1 <= e_dim <= 8, n_e <= 8192, z_ch <= 8, else ENCDIFF_ERR_SHAPE.
+ */
+typedef struct EncdiffVqArgs {
+  int batch, hw, e_dim, n_e;
+  int z_ch, dis_dim;          /* rows: post_quant_conv out channels, width of s_b (0: no concat) */
+  int quantize, pad_;
+  const float* z;             /* fp32 NCHW [batch][e_dim][hw]                               */
+  const float* codebook;      /* fp32 [n_e][e_dim]                                          */
+  const float* table;         /* fp32 T [n_e][z_ch] (rows, quantize)                        */
+  const float* wq;            /* fp32 [z_ch][e_dim] (rows, quantize == 0)                   */
+  const float* wd;            /* fp32 [z_ch][dis_dim]                                       */
+  const float* bias;          /* fp32 [z_ch]                                                */
+  const float* repr;          /* fp32 [batch][dis_dim]; NULL: zeros                         */
+  int* idx;                   /* optional out: int32 [batch*hw]                             */
+  float* zq;                  /* optional out: fp32 NCHW [batch][e_dim][hw]                 */
+  void* rows; long ld_rows;   /* optional out: bf16 [batch*hw][ld_rows], channels z_ch..7 zero */
+} EncdiffVqArgs;
+
+int encdiff_vq_lookup(const EncdiffVqArgs* args, void* stream);
+
 /* Library/device information (for tests): returns the number of exported kernels. */
 int encdiff_version(void);
 
