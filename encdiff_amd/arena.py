@@ -153,8 +153,14 @@ class ParamArena:
         return self.mirror
 
     def enable_ema(self):
+        """The EMA shadow of the arena's first ema_numel elements.  The fused optimizer updates it in
+        float4 lanes (encdiff_adamw_ema: `ema` addressable up to ema_n rounded up to 4), so the storage
+        is rounded up to a multiple of 4 floats (the extra ones stay zero) and `ema` is its
+        [:ema_numel] view."""
         if self.ema is None:
-            self.ema = self.master[: self.ema_numel].clone()
+            self._ema_store = torch.zeros((self.ema_numel + 3) // 4 * 4, device=self.device, dtype=torch.float32)
+            self.ema = self._ema_store[: self.ema_numel]
+            self.ema.copy_(self.master[: self.ema_numel])
         return self.ema
 
 

@@ -48,6 +48,16 @@ __global__ __launch_bounds__(256) void ew_kernel(const EncdiffEwArgs p) {
           da[i] = d[i] * gelu_erf(g[i]);
           dg[i] = d[i] * a[i] * gelu_erf_grad(g[i]);
         }
+        if (p.accumulate) {  // both halves: y += result, as the fp32 kernel
+          float pa[8], pg[8];
+          unpack8(*(const uint4*)(Y + (long)r * p.ldy + c), pa);
+          unpack8(*(const uint4*)(Y + (long)r * p.ldy + p.cols + c), pg);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            da[i] += pa[i];
+            dg[i] += pg[i];
+          }
+        }
         *(uint4*)(Y + (long)r * p.ldy + c) = pack8(da);
         *(uint4*)(Y + (long)r * p.ldy + p.cols + c) = pack8(dg);
         continue;

@@ -470,7 +470,12 @@ int encdiff_ddim_step_indexed(const float* x, const float* e, const float* noise
 /* hyper (device fp32[8], read at execution time so a captured step graph can be
  * replayed with a new lr / step): [lr, beta1, beta2, eps, weight_decay,
  * lr / (1 - beta1^step), 1 / sqrt(1 - beta2^step), ema (1 - decay)].
- * The EMA covers the first ema_n elements of the arena (the UNet parameters). */
+ * The EMA covers the first ema_n elements of the arena (the UNet parameters).
+ * Lengths: n % 4 == 0 and p, g, m, v are 16-byte aligned (the kernel works in float4 lanes).
+ * `ema` (16-byte aligned) must be addressable up to ema_n ROUNDED UP to a multiple of 4 floats:
+ * the lane that holds element ema_n - 1 is loaded and stored whole, and its elements at and
+ * past ema_n are rewritten with their own values (bitwise unchanged).  Nothing past that lane
+ * is touched.  ParamArena.enable_ema() allocates the rounded storage. */
 int encdiff_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, long long n,
                       const float* hyper, long long ema_n, void* stream);
 /* encdiff_adamw_ema that also writes the updated weights as bf16 into `mirror` (n elements,
@@ -521,7 +526,11 @@ int encdiff_grad_fold(const float* dw, int co, int cin, int cpad, int taps, floa
  *   id = perm[(*step mod steps_per_epoch) * batch + b]          (shuffled epoch order)
  * perm: device int64 [steps_per_epoch * batch]; step: device int64 counter (NULL = 0),
  * advanced by one after the gather when `advance` != 0, so a captured step graph walks
- * the epoch by itself. */
+ * the epoch by itself.
+ * An id outside [0, n_images) is clamped to the nearest valid image (id < 0 reads image 0,
+ * id >= n_images reads image n_images - 1): the kernel's bounds guard, never an error.
+ * (h * w) % 4 == 0 and h * w * c <= 65536; images whose byte size is not a multiple of 16 (or
+ * whose address is not 16-byte aligned) are staged byte-wise, the rest with 16-byte loads. */
 int encdiff_gather_images_u8(const void* pool, long long n_images, int h, int w, int c,
                              const long long* perm, long long* step, int steps_per_epoch, int batch,
                              int advance, float* out, void* stream);
