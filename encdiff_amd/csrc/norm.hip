@@ -1,9 +1,18 @@
 // norm.hip -- GroupNorm(+FiLM)(+SiLU) and LayerNorm, forward and backward, NHWC bf16.
 //
-// GroupNorm: one workgroup per (image, slice of whole groups); the slice is held in
-// registers between the statistics (fp32, two-pass, as GroupNorm32 computes in fp32:
-// util.py:242-244) and the write of the normalised, FiLM-modulated, SiLU-activated
-// output (openaimodel_enc.py:201-205, 225-232, 267-271, 684-686; attention.py:76-77).
+// GroupNorm: one workgroup per (image, slice of whole groups); the slice is held in an
+// LDS tile between the statistics (fp32 as GroupNorm32 computes, util.py:242-244, but in ONE
+// pass: sum and sum of squares together, var = E[x^2] - mean^2) and the write of the
+// normalised, FiLM-modulated, SiLU-activated output (openaimodel_enc.py:201-205, 225-232,
+// 267-271, 684-686; attention.py:76-77).
+// Limit of the one-pass variance: the subtraction cancels log2((mean / std)^2) bits, so rstd
+// carries a relative error of about (mean / std)^2 * 2^-24 times a small factor: measured 1e-5
+// at |mean| / std = 16 and 1.3e-4 .. 1.7e-4 at 64 on groups of 192 and 512 elements
+// (tests/test_gpu_norm.py, test_gn_fwd_conditioning), still below bf16's 2^-9 output rounding;
+// towards |mean| / std = 4096 no bit of the variance is left (it is clamped at 0).  The kernels
+// that take the producer's segment sums (in_stats: gn_fwd_stats_kernel, gn_group_stats_kernel)
+// share the limit and cannot avoid it: the sums arrive uncentred.  The fp32 kernels (fp32.hip)
+// are two-pass and hold.
 // The backward recomputes the forward from x and the saved statistics and emits
 // per-image partial sums for dgamma/dbeta (reduced once per step by
 // encdiff_reduce_partials) and the FiLM gradients d(scale), d(shift) per (b, c).
@@ -38,7 +47,7 @@ constexpr int GN_TILE_FWD = 6144;  // forward: dynamic LDS tile up to 96 KB (the
 // Threads: tv = channel vector (8 channels) of the slice, tp = pixel lane.  The slice is
 // read from HBM once into an LDS tile (slices larger than GN_TILE vectors re-read HBM/L2),
 // per-channel partials are reduced deterministically (wave shuffles + ordered LDS sums),
-// statistics are two-pass (mean, then centred sum of squares).  Loops stay rolled (4-way
+// statistics are one-pass (sum and sum of squares in one reduction).  Loops stay rolled (4-way
 // unrolled) so the kernels are a few hundred instructions: a cold instruction cache is
 // otherwise the dominant latency of these small launches.
 // Workgroup -> (image, slice) index, XCD-aware: workgroup i runs on XCD i % 8, and the slices of

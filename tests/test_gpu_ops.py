@@ -679,7 +679,8 @@ def test_groupnorm(O, C, H, film, silu, eps):
             assert rel(dE2[:, :2 * C], Er.grad[:, :2 * C]) < 5e-3
 
 
-@pytest.mark.parametrize("rows,C", [(32768, 64), (8192, 128), (2048, 256), (512, 256), (1000, 128)])
+@pytest.mark.parametrize("rows,C", [(32768, 64), (8192, 128), (2048, 256), (512, 256), (1000, 128),
+                                    (1000, 512)])
 def test_layernorm(O, rows, C):
     torch.manual_seed(4)
     x = (torch.randn(rows, C, device=dev) + 0.3).to(torch.bfloat16)
