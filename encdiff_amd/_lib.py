@@ -192,6 +192,13 @@ class VqArgs(C.Structure):
                 ("idx", vp), ("zq", vp), ("rows", vp), ("ld_rows", C.c_long)]
 
 
+class SamplerStepArgs(C.Structure):
+    _fields_ = [("batch", C.c_int), ("c", C.c_int), ("hw", C.c_int), ("n_e", C.c_int), ("clamp", C.c_int),
+                ("advance", C.c_int), ("coef_host", C.c_float * 5), ("pad_", C.c_int),
+                ("x", vp), ("e", vp), ("noise", vp), ("coef", vp), ("index", vp), ("codebook", vp),
+                ("x_out", vp), ("x0_out", vp), ("idx_out", vp)]
+
+
 _PROTOS = {
     "encdiff_gemm": [C.POINTER(GemmArgs), vp],
     "encdiff_gemm_pair": [C.POINTER(GemmArgs), C.POINTER(GemmArgs), vp],
@@ -252,6 +259,9 @@ _PROTOS = {
     "encdiff_resconv_query": [C.POINTER(ResConvArgs), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "encdiff_step_prologue": [C.POINTER(StepPrologueArgs), vp],
     "encdiff_vq_lookup": [C.POINTER(VqArgs), vp],
+    "encdiff_masked_renoise": [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp],
+    "encdiff_ddim_step_quantized": [C.POINTER(SamplerStepArgs), vp],
+    "encdiff_ancestral_step": [C.POINTER(SamplerStepArgs), vp],
     "encdiff_version": [],
 }
 

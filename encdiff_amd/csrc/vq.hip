@@ -2,21 +2,13 @@
 // autoencoder.py VQModelInterface.decode), the quantised latent, and the decoder's input rows
 // post_quant_conv(cat(z_q, s_b)) in one launch.
 //
-// The distance is evaluated directly, sum_c (z_c - E_jc)^2 in fp32 (not the expanded
-// |z|^2 + |e|^2 - 2 z.e form: its cancellation costs digits exactly where two codes are close).
-// The codebook is staged in LDS channel-major ([c][code]) in chunks of VQ_LDS_FLOATS: with one
-// lane per row all lanes read one address (a broadcast), with `split` lanes per row the lanes of a
-// row read consecutive dwords (no bank conflict).  A row's lanes scan codes sub, sub + split, ...
-// in ascending order with a strict <, and are reduced by (distance, index) order, so ties go to
-// the lowest index.  The 1x1 post_quant_conv is linear: rows = T[idx] + Wd s_b + b with
-// T = E Wpq[:, :e_dim]^T composed by the caller.
-#include "common.h"
+// The search (direct fp32 distance, channel-major LDS chunks, lanes split per row, ties to the
+// lowest index) is vq_search.h, shared with the quantised-x0 sampling steps.  The 1x1
+// post_quant_conv is linear: rows = T[idx] + Wd s_b + b with T = E Wpq[:, :e_dim]^T composed by
+// the caller.
+#include "vq_search.h"
 
 namespace {
-
-constexpr int VQ_T = 256;
-constexpr int VQ_LDS_FLOATS = 8192;  // 32 KB: the 2048 x 3 codebook in one chunk
-constexpr int VQ_MAX_DIM = 8;
 
 template <int ED>
 __global__ __launch_bounds__(VQ_T) void vq_lookup_kernel(const EncdiffVqArgs p, const int split, const int chunk) {
@@ -33,35 +25,7 @@ __global__ __launch_bounds__(VQ_T) void vq_lookup_kernel(const EncdiffVqArgs p, 
 #pragma unroll
   for (int c = 0; c < ED; ++c) z[c] = p.z[(b * ED + c) * p.hw + px];
 
-  int best = 0;
-  if (p.quantize) {
-    float bd = __builtin_inff();
-    int bj = 0x7fffffff;
-    for (int j0 = 0; j0 < p.n_e; j0 += chunk) {
-      const int n = min(chunk, p.n_e - j0);
-      if (j0) __syncthreads();  // the previous chunk is consumed
-      for (int i = threadIdx.x; i < n * ED; i += VQ_T) {
-        const int j = i / ED, c = i - j * ED;
-        cb[c * chunk + j] = p.codebook[(long)j0 * ED + i];
-      }
-      __syncthreads();
-      for (int j = sub; j < n; j += split) {
-        float d = 0.f;
-#pragma unroll
-        for (int c = 0; c < ED; ++c) {
-          const float t = z[c] - cb[c * chunk + j];
-          d += t * t;
-        }
-        if (d < bd) { bd = d; bj = j0 + j; }
-      }
-    }
-    for (int o = split >> 1; o > 0; o >>= 1) {
-      const float od = __shfl_xor(bd, o, 64);
-      const int oj = __shfl_xor(bj, o, 64);
-      if (od < bd || (od == bd && oj < bj)) { bd = od; bj = oj; }
-    }
-    best = (bj >= 0 && bj < p.n_e) ? bj : 0;  // no finite distance (NaN input): entry 0
-  }
+  const int best = p.quantize ? vq_search<ED>(z, cb, p.codebook, p.n_e, split, sub, chunk) : 0;
   if (!live || sub) return;
 
   if (p.idx) p.idx[row] = best;
@@ -111,7 +75,7 @@ extern "C" int encdiff_vq_lookup(const EncdiffVqArgs* a, void* stream) {
   if (total * VQ_MAX_DIM >= (1L << 31)) return ENCDIFF_ERR_SHAPE;
   if (a->quantize) {
     if (!a->codebook) return ENCDIFF_ERR_ARG;
-    if (a->n_e < 1 || a->n_e > 8192) return ENCDIFF_ERR_SHAPE;
+    if (a->n_e < 1 || a->n_e > VQ_MAX_CODES) return ENCDIFF_ERR_SHAPE;
     if (a->rows && !a->table) return ENCDIFF_ERR_ARG;
   } else {
     if (a->idx || a->zq) return ENCDIFF_ERR_ARG;  // nothing was looked up
@@ -122,11 +86,7 @@ extern "C" int encdiff_vq_lookup(const EncdiffVqArgs* a, void* stream) {
     if (!a->bias || (a->dis_dim > 0 && a->repr && !a->wd)) return ENCDIFF_ERR_ARG;
     if (a->ld_rows < 8 || a->ld_rows % 8 || ((uintptr_t)a->rows % 16)) return ENCDIFF_ERR_ARG;  // one 16-byte store
   }
-  // lanes per row: a workgroup per CU at small batches (B = 4 at 16 x 16 is 1024 rows: 64 lanes
-  // per row, 256 workgroups), never more lanes than a wave or than codes
-  int split = 1;
-  if (a->quantize)
-    while (split < 64 && 2 * split <= a->n_e && total * split < 256L * VQ_T) split *= 2;
+  const int split = a->quantize ? vq_split(total, a->n_e) : 1;
   hipStream_t s = (hipStream_t)stream;
   switch (a->e_dim) {
     case 1: return vq_launch<1>(*a, split, s);

@@ -4,8 +4,8 @@ Same schedule construction (make_schedule, :24-54), same sampling loop order and
 noise consumption (one N(0, I) draw of x's shape per step, :201), same update
 (p_sample_ddim, :188-207) -- the update itself is one HIP kernel.
 
-With ``use_graph=True`` (default on a HIP device, when no per-step callbacks, masks or
-guidance are requested) the WHOLE S-step loop -- S x (UNet forward + DDIM update), plus
+With ``use_graph=True`` (default on a HIP device, when no per-step callbacks or guidance are
+requested) the WHOLE S-step loop -- S x (UNet forward + DDIM update), plus
 the copies of the logged intermediates -- is captured into one HIP graph per (batch shape,
 S, eta, log_every_t) and replayed once per ``sample()`` call.  Everything the graph reads
 lives in buffers owned by its cache entry (x_T, the conditioning, the per-step noise table,
@@ -20,6 +20,14 @@ graph-safe Philox stream advances on every replay), so a loop holds one step's n
 given table instead -- step i (in loop order, i = 0 .. S-1) adds sigma_i * normals_sequence[i]
 -- which is how the eta > 0 trajectory is pinned against the reference's CPU noise stream.
 At eta == 0 sigma is 0 for every step and no noise is drawn.
+
+Inpainting (``mask`` + ``x0``) and ``quantize_x0`` run on the same captured paths: a masked step
+re-noises the known region in front of the UNet (ops.masked_renoise, its N(0, I) row drawn inside
+the graph, or taken from ``mask_normals_sequence`` -- S draws of x's shape in loop order, the
+counterpart of ``normals_sequence``), a quantised step replaces pred_x0 by its nearest codebook
+entry inside the update kernel (ops.ddim_step_quantized).  The mask and x0 live in buffers of the
+cache entry like x_T and the conditioning.  The logged intermediates are the un-blended values
+and the final sample is not blended, as in the reference's loop.
 
 Before a replay the model's bf16 weight packs are refreshed if the parameters changed in
 place since the capture (LatentDiffusion.refresh_hip_weights): a sampler captured outside
@@ -95,7 +103,8 @@ class DDIMSampler(object):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None,
                img_callback=None, quantize_x0=False, eta=0., mask=None, x0=None, temperature=1.,
                noise_dropout=0., score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None,
-               log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None, **kwargs):
+               log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None,
+               mask_normals_sequence=None, **kwargs):
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         C, H, W = shape
         size = (batch_size, C, H, W)
@@ -105,13 +114,14 @@ class DDIMSampler(object):
                                   corrector_kwargs=corrector_kwargs, x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning,
-                                  normals_sequence=normals_sequence)
+                                  normals_sequence=normals_sequence, mask_normals_sequence=mask_normals_sequence)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
-                      unconditional_guidance_scale=1., unconditional_conditioning=None, normals_sequence=None):
+                      unconditional_guidance_scale=1., unconditional_conditioning=None, normals_sequence=None,
+                      mask_normals_sequence=None):
         device = self.model.betas.device
         b = shape[0]
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float().contiguous()
@@ -125,24 +135,42 @@ class DDIMSampler(object):
         total = steps.shape[0]
         if normals_sequence is not None:
             normals_sequence = self._noise_table(normals_sequence, total, img.shape, device)
+        if mask_normals_sequence is not None:
+            mask_normals_sequence = self._noise_table(mask_normals_sequence, total, img.shape, device,
+                                                      "mask_normals_sequence")
         intermediates = {"x_inter": [img], "pred_x0": [img]}
-        simple = (callback is None and img_callback is None and mask is None and not quantize_denoised and
+        kmask = None  # the mask in the re-noise kernel's layout, (B, 1, H, W) or (B, C, H, W)
+        if mask is not None:
+            assert x0 is not None, "inpainting needs x0 with the mask"
+            kmask = self._kernel_mask(mask, img)
+        simple = (callback is None and img_callback is None and (mask is None or kmask is not None) and
+                  (not quantize_denoised or self._codebook(img) is not None) and
                   noise_dropout == 0. and score_corrector is None and temperature == 1. and
                   (unconditional_conditioning is None or unconditional_guidance_scale == 1.))
         if self.use_graph and simple and img.is_cuda and timesteps is None and isinstance(cond, torch.Tensor):
+            extra = dict(mask=kmask, x0=x0, quant=bool(quantize_denoised), mask_normals=mask_normals_sequence)
             if total <= GRAPH_MAX_STEPS:
                 lk = (tuple(img.shape), total, self._sched_key, tuple(cond.shape), cond.dtype, log_every_t,
-                      bool(normals_sequence is not None and self.ddim_eta))
+                      bool(normals_sequence is not None and self.ddim_eta),
+                      None if kmask is None else (tuple(kmask.shape), mask_normals_sequence is not None),
+                      bool(quantize_denoised))
                 seen = self._seen.get(lk, 0)
                 self._seen[lk] = seen + 1
                 if seen >= LOOP_GRAPH_AFTER:
-                    return self._loop_graph(cond, img, total, log_every_t, intermediates, normals_sequence)
-            return self._step_graph(cond, img, total, log_every_t, intermediates, normals_sequence)
+                    return self._loop_graph(cond, img, total, log_every_t, intermediates, normals_sequence, **extra)
+            return self._step_graph(cond, img, total, log_every_t, intermediates, normals_sequence, **extra)
         for i, step in enumerate(np.flip(steps)):
             index = total - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
             if mask is not None:
-                img = self.model.q_sample(x0, ts) * mask + (1. - mask) * img
+                mz = None if mask_normals_sequence is None else mask_normals_sequence[i]
+                if kmask is not None and img.is_cuda:  # the captured loops' kernel
+                    img = img.clone()  # the caller's x_T / a logged (un-blended) intermediate stays as it is
+                    ops.masked_renoise(img, x0.float().contiguous(), torch.randn_like(img) if mz is None else mz,
+                                       kmask, ts, self.model.sqrt_alphas_cumprod,
+                                       self.model.sqrt_one_minus_alphas_cumprod)
+                else:
+                    img = self.model.q_sample(x0, ts, noise=mz) * mask + (1. - mask) * img
             img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, quantize_denoised=quantize_denoised,
                                               temperature=temperature, noise_dropout=noise_dropout,
                                               score_corrector=score_corrector, corrector_kwargs=corrector_kwargs,
@@ -159,12 +187,34 @@ class DDIMSampler(object):
         return img, intermediates
 
     @staticmethod
-    def _noise_table(seq, total, shape, device):
+    def _noise_table(seq, total, shape, device, what="normals_sequence"):
         t = torch.stack(list(seq)) if not isinstance(seq, torch.Tensor) else seq
         t = t.to(device=device, dtype=torch.float32).contiguous()
         if t.shape[0] < total or tuple(t.shape[1:]) != tuple(shape):
-            raise ValueError(f"normals_sequence must hold {total} draws of shape {tuple(shape)}, got {tuple(t.shape)}")
+            raise ValueError(f"{what} must hold {total} draws of shape {tuple(shape)}, got {tuple(t.shape)}")
         return t
+
+    @staticmethod
+    def _kernel_mask(mask, img):
+        """mask as fp32 (B, 1, H, W) or (B, C, H, W) on img's device; None: another broadcast shape
+        (the torch expression of the eager loop handles it)."""
+        if not isinstance(mask, torch.Tensor) or mask.dim() != 4:
+            return None
+        B, C, H, W = img.shape
+        if tuple(mask.shape) not in ((B, 1, H, W), (B, C, H, W)):
+            return None
+        return mask.to(device=img.device, dtype=torch.float32).contiguous()
+
+    def _codebook(self, img):
+        """The first stage's codebook [n_e][e_dim] when the quantised-x0 kernel covers it (a VQ
+        first stage, e_dim == the latent's channels, within the kernel's limits), else None."""
+        q = getattr(getattr(self.model, "first_stage_model", None), "quantize", None)
+        w = getattr(getattr(q, "embedding", None), "weight", None)
+        if w is None or not img.is_cuda or w.dim() != 2 or w.shape[1] != img.shape[1]:
+            return None
+        if not ops.vq_supported(w.shape[0], w.shape[1]) or w.dtype != torch.float32 or not w.is_contiguous():
+            return None
+        return w.detach()
 
     @torch.no_grad()
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
@@ -189,7 +239,12 @@ class DDIMSampler(object):
             noise = torch.nn.functional.dropout(noise, p=noise_dropout)
         x = x.float().contiguous()
         e_t = e_t.float().contiguous()
-        if quantize_denoised:
+        cb = self._codebook(x) if quantize_denoised else None
+        if cb is not None:
+            x_prev, pred_x0 = torch.empty_like(x), torch.empty_like(x)
+            ops.ddim_step_quantized(x, e_t, noise.float().contiguous(), (a_t, a_prev, sigma, s1), cb, x_prev, pred_x0)
+            return x_prev, pred_x0
+        if quantize_denoised:  # a codebook outside the kernel's limits: the torch quantiser
             pred_x0 = (x - s1 * e_t) / np.sqrt(a_t)
             pred_x0, _, _ = self.model.first_stage_model.quantize(pred_x0)
             x_prev = np.sqrt(a_prev) * pred_x0 + np.sqrt(1. - a_prev - sigma ** 2) * e_t + sigma * noise
@@ -197,12 +252,16 @@ class DDIMSampler(object):
         return torch.ops.encdiff.ddim_step(x, e_t, noise, a_t, a_prev, sigma, s1)
 
     # ------------------------------------------------------------ captured loops
-    def _entry(self, kind, cond, img, total, log_every_t, injected):
+    def _entry(self, kind, cond, img, total, log_every_t, injected, mask=None, x0=None, quant=False,
+               mask_normals=None):
         """Cache entry (static input / output buffers) of a captured loop.  ``injected``: the
-        noise comes from a caller's normals_sequence table (else drawn inside the graph)."""
+        noise comes from a caller's normals_sequence table (else drawn inside the graph).  mask /
+        x0: inpainting (buffers of the entry, copied in per call; mask_normals: the re-noise table
+        is injected too); quant: pred_x0 is quantised."""
         injected = bool(injected and self.ddim_eta)
+        mkey = None if mask is None else (tuple(mask.shape), mask_normals is not None)
         key = (kind, tuple(img.shape), total, self._sched_key, tuple(cond.shape), cond.dtype, log_every_t,
-               injected)
+               injected, mkey, bool(quant))
         st = self._graphs.get(key)
         if st is None:
             dev = img.device
@@ -212,10 +271,19 @@ class DDIMSampler(object):
                       log_x=torch.empty(len(logs), *img.shape, device=dev),
                       log_px0=torch.empty(len(logs), *img.shape, device=dev),
                       noise=torch.zeros((total if injected else 1), *img.shape, device=dev),
-                      draw=bool(self.ddim_eta) and not injected, graph=None)
+                      draw=bool(self.ddim_eta) and not injected, graph=None, mask=None,
+                      codebook=self._codebook(img) if quant else None)
+            if mask is not None:
+                st.update(mask=torch.empty_like(mask), x0=torch.empty_like(img), mdraw=mask_normals is None,
+                          mnoise=torch.zeros((1 if mask_normals is None else total), *img.shape, device=dev))
             self._graphs[key] = st
         st["cond"].copy_(cond)
         st["x"].copy_(img)
+        if mask is not None:
+            st["mask"].copy_(mask)
+            st["x0"].copy_(x0)
+            if mask_normals is not None:
+                st["mnoise"].copy_(mask_normals[:total])
         return st
 
     def _fill_noise(self, st, normals_sequence, total):
@@ -227,10 +295,10 @@ class DDIMSampler(object):
         if f is not None:
             f()
 
-    def _loop_graph(self, cond, img, total, log_every_t, intermediates, normals_sequence):
+    def _loop_graph(self, cond, img, total, log_every_t, intermediates, normals_sequence, **extra):
         """The whole loop as one HIP graph (unrolled: step i's coefficients and timestep are
         kernel arguments / a static timestep row)."""
-        st = self._entry("loop", cond, img, total, log_every_t, normals_sequence is not None)
+        st = self._entry("loop", cond, img, total, log_every_t, normals_sequence is not None, **extra)
         self._fill_noise(st, normals_sequence, total)
         self._refresh()
         if st["graph"] is None:
@@ -296,13 +364,19 @@ class DDIMSampler(object):
             index = total - i - 1
             if ex is not None:
                 ex.samp_i = i
+            if st["mask"] is not None:
+                self._renoise(st, x, st["ts"][i], st["mnoise"][i if st["mnoise"].shape[0] > 1 else 0])
             e_t = self.model.apply_model(x, st["ts"][i], st["cond"])
             a_t, a_prev = float(self.ddim_alphas[index]), float(self.ddim_alphas_prev[index])
             sigma, s1 = float(self.ddim_sigmas[index]), float(self.ddim_sqrt_one_minus_alphas[index])
             if st["draw"]:
                 st["noise"][0].normal_()
-            ops.ddim_step(x, e_t.float().contiguous(), st["noise"][i if noise_n > 1 else 0], a_t, a_prev, sigma, s1,
-                          xn, st["px0"])
+            z = st["noise"][i if noise_n > 1 else 0]
+            if st["codebook"] is not None:
+                ops.ddim_step_quantized(x, e_t.float().contiguous(), z, (a_t, a_prev, sigma, s1), st["codebook"], xn,
+                                        st["px0"])
+            else:
+                ops.ddim_step(x, e_t.float().contiguous(), z, a_t, a_prev, sigma, s1, xn, st["px0"])
             x, xn = xn, x
             if i in logs:
                 j = logs.index(i)
@@ -310,17 +384,25 @@ class DDIMSampler(object):
                 st["log_px0"][j].copy_(st["px0"])
         st["out"] = x
 
-    def _step_graph(self, cond, img, total, log_every_t, intermediates, normals_sequence):
+    def _renoise(self, st, x, t_row, z):
+        """Kernel (a) in front of the UNet: the known region of x re-noised to the step's t."""
+        if st["mdraw"]:
+            z.normal_()
+        ops.masked_renoise(x, st["x0"], z, st["mask"], t_row, self.model.sqrt_alphas_cumprod,
+                           self.model.sqrt_one_minus_alphas_cumprod)
+
+    def _step_graph(self, cond, img, total, log_every_t, intermediates, normals_sequence, **extra):
         """Loops longer than GRAPH_MAX_STEPS: one captured step (coefficients, timestep and
         noise row looked up at a device step index), replayed S times."""
-        st = self._entry("step", cond, img, total, log_every_t, normals_sequence is not None)
+        st = self._entry("step", cond, img, total, log_every_t, normals_sequence is not None, **extra)
         self._fill_noise(st, normals_sequence, total)
         self._refresh()
         b = img.shape[0]
         if st["graph"] is None:
             dev = img.device
             st.update(t=torch.empty(b, device=dev, dtype=torch.long), idx=torch.zeros(1, device=dev, dtype=torch.int32),
-                      i=torch.zeros(1, device=dev, dtype=torch.long), zrow=torch.empty_like(img))
+                      i=torch.zeros(1, device=dev, dtype=torch.long), zrow=torch.empty_like(img),
+                      mzrow=torch.empty_like(img))
             x0 = st["x"].clone()
             st["idx"].fill_(total - 1)
             self._step_body(st)
@@ -346,6 +428,13 @@ class DDIMSampler(object):
     def _step_body(self, st):
         idx = st["idx"]
         st["t"].copy_(self._ts.index_select(0, idx.long()).expand(st["t"].shape[0]))
+        if st["mask"] is not None:
+            if st["mnoise"].shape[0] > 1:  # re-noise row of loop step i (device counter)
+                st["mzrow"].copy_(st["mnoise"].index_select(0, st["i"]).view_as(st["mzrow"]))
+                mz = st["mzrow"]
+            else:
+                mz = st["mnoise"][0]
+            self._renoise(st, st["x"], st["t"], mz)
         um = self._borrow(True)
         try:
             e_t = self.model.apply_model(st["x"], st["t"], st["cond"])
@@ -354,12 +443,17 @@ class DDIMSampler(object):
                 um.borrow_eps = False
         if st["noise"].shape[0] > 1:  # noise row of loop step i (device counter)
             st["zrow"].copy_(st["noise"].index_select(0, st["i"]).view_as(st["zrow"]))
-            st["i"].add_(1)
             z = st["zrow"]
         else:
             z = st["noise"][0]
             if st["draw"]:
                 z.normal_()
-        ops.ddim_step_indexed(st["x"], e_t.float().contiguous(), z, self._coef, idx, st["x2"], st["px0"],
-                              advance=True)
+        if st["noise"].shape[0] > 1 or (st["mask"] is not None and st["mnoise"].shape[0] > 1):
+            st["i"].add_(1)  # the device counter of the injected tables
+        if st["codebook"] is not None:
+            ops.ddim_step_quantized(st["x"], e_t.float().contiguous(), z, self._coef, st["codebook"], st["x2"],
+                                    st["px0"], index=idx, advance=True)
+        else:
+            ops.ddim_step_indexed(st["x"], e_t.float().contiguous(), z, self._coef, idx, st["x2"], st["px0"],
+                                  advance=True)
         st["x"].copy_(st["x2"])

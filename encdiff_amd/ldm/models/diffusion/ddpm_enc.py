@@ -8,7 +8,9 @@ scale_factor), same methods on the path: register_schedule (:133-187),
 q_sample (:292-295), get_input (:773-844), forward (:1040-1053),
 apply_model (:1065-1163), p_losses (:1183-1253), training_step (:360-375),
 on_train_batch_end / EMA (:399-401), configure_optimizers (:1598-1639),
-sample_log (:1442-1455), log_images (:1473-1596, sampling subset).
+predict_start_from_noise / q_posterior (:234-247), p_mean_variance / p_sample (:1255-1315),
+progressive_denoising / p_sample_loop / sample (:1317-1440), sample_log (:1442-1455),
+log_images (:1473-1596).
 
 The modules are plain nn.Modules (no Lightning dependency); ``training_step`` returns
 the loss and keeps the reference's log dict in ``self.last_log``.  q_sample, the UNet,
@@ -292,6 +294,30 @@ class DDPM(nn.Module):
         return torch.ops.encdiff.q_sample(x_start, noise, t, self.sqrt_alphas_cumprod,
                                           self.sqrt_one_minus_alphas_cumprod)
 
+    def predict_start_from_noise(self, x_t, t, noise):
+        """ddpm_enc.py:234-238."""
+        return (extract_into_tensor(self.sqrt_recip_alphas_cumprod, t, x_t.shape) * x_t -
+                extract_into_tensor(self.sqrt_recipm1_alphas_cumprod, t, x_t.shape) * noise)
+
+    def q_posterior(self, x_start, x_t, t):
+        """ddpm_enc.py:240-247."""
+        mean = (extract_into_tensor(self.posterior_mean_coef1, t, x_t.shape) * x_start +
+                extract_into_tensor(self.posterior_mean_coef2, t, x_t.shape) * x_t)
+        return (mean, extract_into_tensor(self.posterior_variance, t, x_t.shape),
+                extract_into_tensor(self.posterior_log_variance_clipped, t, x_t.shape))
+
+    def ancestral_table(self):
+        """Device table [T][5] of ops.ancestral_step, row t = (sqrt_recip_alphas_cumprod,
+        sqrt_recipm1_alphas_cumprod, posterior_mean_coef1, posterior_mean_coef2,
+        posterior_log_variance_clipped)[t].  Built once per device from the registered buffers and
+        kept: captured steps hold its address."""
+        tab = getattr(self, "_anc_table", None)
+        if tab is None or tab.device != self.betas.device:
+            tab = self._anc_table = torch.stack(
+                [self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod, self.posterior_mean_coef1,
+                 self.posterior_mean_coef2, self.posterior_log_variance_clipped], dim=1).float().contiguous()
+        return tab
+
     def get_loss(self, pred, target, mean=True):
         if self.loss_type == "l1":
             loss = (target - pred).abs()
@@ -322,6 +348,13 @@ class DDPM(nn.Module):
 
 class LatentDiffusion(DDPM):
     """ddpm_enc.py:482-1648 (EncDiff path)."""
+
+    # log_images also runs the reference's quantised-x0, inpainting / outpainting, denoise and
+    # progressive rows (ENCDIFF_LOG_IMAGES_FULL=1 sets it in setup_hip_training)
+    log_images_full = False
+    # the ancestral loops replay one captured step where nothing needs the host between steps
+    # (False: always launch the kernels step by step)
+    ancestral_use_graph = True
 
     def __init__(self, first_stage_config, cond_stage_config, num_timesteps_cond=None, cond_stage_key="image",
                  cond_stage_trainable=False, concat_mode=True, cond_stage_forward=None, conditioning_key=None,
@@ -534,6 +567,8 @@ class LatentDiffusion(DDPM):
         if self.use_ema:
             self.model_ema.bind_arena(arena, prefix="model.")
             self._ema_fused = True
+        if os.environ.get("ENCDIFF_LOG_IMAGES_FULL", "0") == "1":
+            self.log_images_full = True
         self._arena = arena
         return arena
 
@@ -568,7 +603,7 @@ class LatentDiffusion(DDPM):
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, **kwargs):
         if not ddim:
-            raise NotImplementedError("ancestral p_sample loop is not on the EncDiff path; use ddim=True")
+            return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True, **kwargs)
         sampler = self.ddim_sampler()
         shape = (self.channels, self.image_size, self.image_size)
         return sampler.sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
@@ -595,6 +630,279 @@ class LatentDiffusion(DDPM):
         samples, _ = sampler.sample(ddim_steps, lu * n, shape, cond.reshape(lu * n, -1), eta=eta, verbose=False,
                                     x_T=x_T, normals_sequence=normals_sequence)
         return samples
+
+    # ------------------------------------------------------------ ancestral sampling
+    def p_mean_variance(self, x, c, t, clip_denoised: bool, return_codebook_ids=False, quantize_denoised=False,
+                        return_x0=False, score_corrector=None, corrector_kwargs=None):
+        """ddpm_enc.py:1255-1284, the reference's expressions around the HIP UNet (per-sample t).
+        The sampling loops below do not come through here: their update is ops.ancestral_step."""
+        if return_codebook_ids:
+            raise DeprecationWarning("Support dropped.")
+        model_out = self.apply_model(x, t, c).float()
+        if score_corrector is not None:
+            assert self.parameterization == "eps"
+            model_out = score_corrector.modify_score(self, model_out, x, t, c, **corrector_kwargs)
+        if self.parameterization == "eps":
+            x_recon = self.predict_start_from_noise(x, t=t, noise=model_out)
+        elif self.parameterization == "x0":
+            x_recon = model_out
+        else:
+            raise NotImplementedError()
+        if clip_denoised:
+            x_recon.clamp_(-1., 1.)
+        if quantize_denoised:
+            x_recon, _, _ = self.first_stage_model.quantize(x_recon)
+        model_mean, posterior_variance, posterior_log_variance = self.q_posterior(x_start=x_recon, x_t=x, t=t)
+        if return_x0:
+            return model_mean, posterior_variance, posterior_log_variance, x_recon
+        return model_mean, posterior_variance, posterior_log_variance
+
+    @torch.no_grad()
+    def p_sample(self, x, c, t, clip_denoised=False, repeat_noise=False, return_codebook_ids=False,
+                 quantize_denoised=False, return_x0=False, temperature=1., noise_dropout=0., score_corrector=None,
+                 corrector_kwargs=None):
+        """ddpm_enc.py:1286-1315 for a free-standing call (per-sample t, torch expressions)."""
+        from ...modules.diffusionmodules.util import noise_like
+        b = x.shape[0]
+        outputs = self.p_mean_variance(x=x, c=c, t=t, clip_denoised=clip_denoised,
+                                       return_codebook_ids=return_codebook_ids, quantize_denoised=quantize_denoised,
+                                       return_x0=return_x0, score_corrector=score_corrector,
+                                       corrector_kwargs=corrector_kwargs)
+        model_mean, model_log_variance = outputs[0], outputs[2]
+        noise = noise_like(x.shape, x.device, repeat_noise) * temperature
+        if noise_dropout > 0.:
+            noise = torch.nn.functional.dropout(noise, p=noise_dropout)
+        nonzero_mask = (1 - (t == 0).float()).reshape(b, *((1,) * (len(x.shape) - 1)))  # no noise when t == 0
+        out = model_mean + nonzero_mask * (0.5 * model_log_variance).exp() * noise
+        return (out, outputs[3]) if return_x0 else out
+
+    def _ancestral_codebook(self, x):
+        """The codebook for ops.ancestral_step's quantisation (the sampler's rule)."""
+        cb = self.ddim_sampler()._codebook(x)
+        if cb is None:
+            raise NotImplementedError("quantize_denoised needs a VQ first stage whose codebook the HIP search "
+                                      "covers (e_dim == latent channels <= 8, n_e <= 8192)")
+        return cb
+
+    def _ancestral_loop(self, cond, img, timesteps, log_every_t, log_x0, quantize_denoised=False, mask=None,
+                        x0=None, temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
+                        callback=None, img_callback=None, normals_sequence=None, mask_normals_sequence=None,
+                        use_graph=True):
+        """The loop of p_sample_loop / progressive_denoising (ddpm_enc.py:1350-1371, 1401-1419) from
+        t = timesteps - 1 down to 0: UNet forward, ops.ancestral_step, and for inpainting
+        ops.masked_renoise of the known region at the same t.  log_x0: log x0_partial (progressive)
+        instead of the sample.  One captured step replayed `timesteps` times when nothing needs the
+        host between steps, else the same kernels launched step by step.  Returns (img, logged)."""
+        if self.parameterization != "eps":
+            raise NotImplementedError("the HIP ancestral step covers the eps parameterisation")
+        if not img.is_cuda:
+            raise RuntimeError("the ancestral sampling loop runs on the HIP path")
+        from .ddim import DDIMSampler
+        img = img.float().contiguous()
+        b = img.shape[0]
+        kmask = None
+        if mask is not None:
+            assert x0 is not None
+            kmask = DDIMSampler._kernel_mask(mask, img)
+            if kmask is None:
+                raise NotImplementedError(f"mask of shape {tuple(mask.shape)}: (B, 1, H, W) or (B, C, H, W) expected")
+            x0 = x0.to(img.device).float().contiguous()
+        table = lambda seq, what: None if seq is None else DDIMSampler._noise_table(  # noqa: E731
+            seq, timesteps, img.shape, img.device, what)
+        normals = table(normals_sequence, "normals_sequence")
+        mnormals = table(mask_normals_sequence, "mask_normals_sequence")
+        temps = temperature if isinstance(temperature, (list, tuple)) else None
+        cb = self._ancestral_codebook(img) if quantize_denoised else None
+        plain = (callback is None and img_callback is None and noise_dropout == 0. and score_corrector is None and
+                 (all(tt == 1. for tt in temps) if temps is not None else temperature == 1.))
+        logs = lambda i: i % log_every_t == 0 or i == timesteps - 1  # noqa: E731
+        if use_graph and plain and isinstance(cond, torch.Tensor) and timesteps > 0:
+            return self._ancestral_graph(cond, img, timesteps, logs, log_x0, cb, kmask, x0, normals, mnormals)
+        x = img.clone()
+        xr = torch.empty_like(x)
+        idx = torch.zeros(1, device=x.device, dtype=torch.int32)
+        tab = self.ancestral_table()
+        out = []
+        for k, i in enumerate(reversed(range(timesteps))):
+            ts = torch.full((b,), i, device=x.device, dtype=torch.long)
+            idx.fill_(i)
+            e = self.apply_model(x, ts, cond).float().contiguous()
+            if score_corrector is not None:
+                e = score_corrector.modify_score(self, e, x, ts, cond, **corrector_kwargs).float().contiguous()
+            z = torch.randn_like(x) if normals is None else normals[k]
+            temp = temps[i] if temps is not None else temperature
+            if temp != 1.:
+                z = z * temp
+            if noise_dropout > 0.:
+                z = torch.nn.functional.dropout(z, p=noise_dropout)
+            nxt = torch.empty_like(x)
+            ops.ancestral_step(x, e, z, tab, idx, nxt, xr, clamp=self.clip_denoised, advance=False, codebook=cb)
+            x = nxt
+            if kmask is not None:
+                ops.masked_renoise(x, x0, torch.randn_like(x) if mnormals is None else mnormals[k], kmask, ts,
+                                   self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod)
+            if logs(i):
+                out.append((xr if log_x0 else x).clone())
+            if callback:
+                callback(i)
+            if img_callback:
+                img_callback(x, i)
+        return x, out
+
+    def _ancestral_graph(self, cond, img, timesteps, logs, log_x0, cb, kmask, x0, normals, mnormals):
+        """One captured ancestral step (t, the coefficient row and the injected noise rows looked up
+        at device counters), replayed `timesteps` times.  Buffer discipline of
+        DDIMSampler._step_graph: x, the conditioning, mask and x0 are buffers of the cache entry."""
+        graphs = self.__dict__.setdefault("_anc_graphs", {})
+        key = (tuple(img.shape), tuple(cond.shape), cond.dtype, cb is not None, bool(self.clip_denoised),
+               None if kmask is None else (tuple(kmask.shape), mnormals is not None), normals is not None,
+               timesteps if (normals is not None or mnormals is not None) else 0)
+        st = graphs.get(key)
+        dev = img.device
+        if st is None:
+            st = graphs[key] = dict(
+                x=torch.empty_like(img), xr=torch.empty_like(img), cond=torch.empty_like(cond),
+                t=torch.empty(img.shape[0], device=dev, dtype=torch.long),
+                idx=torch.zeros(1, device=dev, dtype=torch.int32), i=torch.zeros(1, device=dev, dtype=torch.long),
+                noise=torch.zeros((timesteps if normals is not None else 1), *img.shape, device=dev),
+                zrow=torch.empty_like(img), graph=None, codebook=cb, mask=None, tab=self.ancestral_table())
+            if kmask is not None:
+                st.update(mask=torch.empty_like(kmask), x0=torch.empty_like(img), mzrow=torch.empty_like(img),
+                          mnoise=torch.zeros((timesteps if mnormals is not None else 1), *img.shape, device=dev))
+        st["x"].copy_(img)
+        st["cond"].copy_(cond)
+        if normals is not None:
+            st["noise"].copy_(normals[:timesteps])
+        if kmask is not None:
+            st["mask"].copy_(kmask)
+            st["x0"].copy_(x0)
+            if mnormals is not None:
+                st["mnoise"].copy_(mnormals[:timesteps])
+        self.refresh_hip_weights()
+        if st["graph"] is None:
+            keep = st["x"].clone()
+            st["idx"].fill_(timesteps - 1)
+            self._ancestral_body(st)  # warm-up: allocations, kernel attributes, GEMM plans
+            st["x"].copy_(keep)
+            g = torch.cuda.CUDAGraph()
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
+                    self._ancestral_body(st)
+            torch.cuda.current_stream().wait_stream(s)
+            st["graph"] = g
+            st["x"].copy_(keep)
+        st["idx"].fill_(timesteps - 1)
+        st["i"].zero_()
+        out = []
+        for i in reversed(range(timesteps)):
+            st["graph"].replay()
+            if logs(i):
+                out.append((st["xr"] if log_x0 else st["x"]).clone())
+        return st["x"].clone(), out
+
+    def _ancestral_body(self, st):
+        x, idx = st["x"], st["idx"]
+        st["t"].copy_(idx.long().expand(st["t"].shape[0]))  # t is the table row
+        um = self.model.diffusion_model
+        borrow = hasattr(um, "executor")  # the HIP UNet hands its eps buffer over: consumed before the next forward
+        if borrow:
+            um.borrow_eps = True
+        try:
+            e = self.apply_model(x, st["t"], st["cond"])
+        finally:
+            if borrow:
+                um.borrow_eps = False
+
+        def row(table, buf):
+            if table.shape[0] > 1:  # injected: row of loop step i (device counter)
+                buf.copy_(table.index_select(0, st["i"]).view_as(buf))
+                return buf
+            table[0].normal_()
+            return table[0]
+
+        z = row(st["noise"], st["zrow"])
+        ops.ancestral_step(x, e.float().contiguous(), z, st["tab"], idx, x, st["xr"], clamp=self.clip_denoised,
+                           advance=True, codebook=st["codebook"])
+        if st["mask"] is not None:
+            ops.masked_renoise(x, st["x0"], row(st["mnoise"], st["mzrow"]), st["mask"], st["t"],
+                               self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod)
+        st["i"].add_(1)
+
+    @staticmethod
+    def _first(cond, n):
+        if cond is None:
+            return None
+        if isinstance(cond, dict):
+            return {k: (v[:n] if not isinstance(v, list) else [x[:n] for x in v]) for k, v in cond.items()}
+        return [c[:n] for c in cond] if isinstance(cond, list) else cond[:n]
+
+    @torch.no_grad()
+    def progressive_denoising(self, cond, shape, verbose=True, callback=None, quantize_denoised=False,
+                              img_callback=None, mask=None, x0=None, temperature=1., noise_dropout=0.,
+                              score_corrector=None, corrector_kwargs=None, batch_size=None, x_T=None, start_T=None,
+                              log_every_t=None, normals_sequence=None, mask_normals_sequence=None):
+        """ddpm_enc.py:1317-1371: returns (img, [x0_partial at the logged steps]).  normals_sequence /
+        mask_normals_sequence (one draw of x's shape per step, t == 0 included; an extension) inject
+        the step noise / the inpainting re-noise."""
+        log_every_t = log_every_t or self.log_every_t
+        timesteps = self.num_timesteps
+        if batch_size is not None:
+            shape = [batch_size] + list(shape)
+        else:
+            batch_size = shape[0]
+        img = torch.randn(tuple(shape), device=self.device) if x_T is None else x_T
+        cond = self._first(cond, batch_size)
+        if start_T is not None:
+            timesteps = min(timesteps, start_T)
+        if type(temperature) == float:
+            temperature = [temperature] * timesteps
+        return self._ancestral_loop(cond, img, timesteps, log_every_t, True, quantize_denoised=quantize_denoised,
+                                    mask=mask, x0=x0, temperature=temperature, noise_dropout=noise_dropout,
+                                    score_corrector=score_corrector, corrector_kwargs=corrector_kwargs,
+                                    callback=callback, img_callback=img_callback, normals_sequence=normals_sequence,
+                                    mask_normals_sequence=mask_normals_sequence,
+                                    use_graph=self.ancestral_use_graph)
+
+    @torch.no_grad()
+    def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, verbose=True, callback=None,
+                      timesteps=None, quantize_denoised=False, mask=None, x0=None, img_callback=None, start_T=None,
+                      log_every_t=None, normals_sequence=None, mask_normals_sequence=None):
+        """ddpm_enc.py:1373-1422: intermediates = [x_T, the sample at the logged steps]."""
+        log_every_t = log_every_t or self.log_every_t
+        img = torch.randn(tuple(shape), device=self.betas.device) if x_T is None else x_T
+        if timesteps is None:
+            timesteps = self.num_timesteps
+        if start_T is not None:
+            timesteps = min(timesteps, start_T)
+        if mask is not None:
+            assert x0 is not None
+            assert x0.shape[2:3] == mask.shape[2:3]  # spatial size has to match
+        out, inter = self._ancestral_loop(cond, img, timesteps, log_every_t, False,
+                                          quantize_denoised=quantize_denoised, mask=mask, x0=x0, callback=callback,
+                                          img_callback=img_callback, normals_sequence=normals_sequence,
+                                          mask_normals_sequence=mask_normals_sequence,
+                                          use_graph=self.ancestral_use_graph)
+        if return_intermediates:
+            return out, [img] + inter
+        return out
+
+    @torch.no_grad()
+    def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, verbose=True, timesteps=None,
+               quantize_denoised=False, mask=None, x0=None, shape=None, **kwargs):
+        """ddpm_enc.py:1424-1440."""
+        if shape is None:
+            shape = (batch_size, self.channels, self.image_size, self.image_size)
+        return self.p_sample_loop(self._first(cond, batch_size), shape, return_intermediates=return_intermediates,
+                                  x_T=x_T, verbose=verbose, timesteps=timesteps,
+                                  quantize_denoised=quantize_denoised, mask=mask, x0=x0)
+
+    def _get_denoise_row_from_list(self, samples, desc="", force_no_decoder_quantization=False):
+        """ddpm_enc.py:650-660 without the grid: the decoded latents stacked (n_log, B, C, H, W),
+        the convention of diffusion_row."""
+        return torch.stack([self.decode_first_stage(z.to(self.device), force_not_quantize=force_no_decoder_quantization)
+                            for z in samples])
 
     # ------------------------------------------------------------ validation (§8(f) row 4)
     @torch.no_grad()
@@ -665,7 +973,14 @@ class LatentDiffusion(DDPM):
                    quantize_denoised=True, inpaint=True, plot_denoise_rows=False, plot_progressive_rows=True,
                    sample_swap=False, plot_diffusion_rows=True, **kwargs):
         """ddpm_enc.py:1473-1596: inputs, reconstruction, diffusion row, swap samples and samples
-        (DDIM); inpainting / progressive rows are not on the EncDiff path."""
+        (DDIM).  With ``self.log_images_full`` also the reference's remaining rows, each gated by its
+        own flag as there: samples_x0_quantized (quantize_denoised), samples_inpainting /
+        samples_outpainting / mask (inpaint, the centre square), denoise_row (plot_denoise_rows,
+        the logged x_t of the sampling run) and progressive_row (plot_progressive_rows, the
+        x0_partial list of progressive_denoising).  Row outputs are stacked decoded tensors
+        (n_log, B, C, H, W) like diffusion_row, without the reference's torchvision grid."""
+        full = bool(self.log_images_full)
+        use_ddim = ddim_steps is not None
         log = {}
         z, c, x, xrec, xc, orc = self.get_input(batch, self.first_stage_key, return_first_stage_outputs=True,
                                                 force_c_encode=True, return_original_cond=True, bs=N,
@@ -687,8 +1002,35 @@ class LatentDiffusion(DDPM):
                     self.sample_swap(orc, N, ddim_steps=ddim_steps, eta=ddim_eta))
         if sample:
             with self.ema_scope("Plotting"):
-                samples, _ = self.sample_log(cond=c, batch_size=N, ddim=True, ddim_steps=ddim_steps, eta=ddim_eta)
+                samples, z_denoise_row = self.sample_log(cond=c, batch_size=N, ddim=use_ddim, ddim_steps=ddim_steps,
+                                                         eta=ddim_eta)
             log["samples"] = self.decode_first_stage(samples)
+            if full and plot_denoise_rows:
+                if isinstance(z_denoise_row, dict):  # DDIM logs {"x_inter", "pred_x0"}
+                    z_denoise_row = z_denoise_row["x_inter"]
+                log["denoise_row"] = self._get_denoise_row_from_list(z_denoise_row)
+            if full and quantize_denoised and isinstance(self.first_stage_model, VQModelInterface):
+                with self.ema_scope("Plotting Quantized Denoised"):
+                    samples, _ = self.sample_log(cond=c, batch_size=N, ddim=use_ddim, ddim_steps=ddim_steps,
+                                                 eta=ddim_eta, **{"quantize_x0" if use_ddim else "quantize_denoised": True})
+                log["samples_x0_quantized"] = self.decode_first_stage(samples.to(self.device))
+            if full and inpaint:
+                h, w = z.shape[2], z.shape[3]
+                mask = torch.ones(N, h, w, device=self.device)
+                mask[:, h // 4:3 * h // 4, w // 4:3 * w // 4] = 0.  # zeros will be filled in
+                mask = mask[:, None, ...]
+                for name, scope in (("samples_inpainting", "Plotting Inpaint"), ("samples_outpainting", "Plotting Outpaint")):
+                    with self.ema_scope(scope):  # the reference runs the same call twice
+                        samples, _ = self.sample_log(cond=c, batch_size=N, ddim=use_ddim, eta=ddim_eta,
+                                                     ddim_steps=ddim_steps, x0=z[:N], mask=mask)
+                    log[name] = self.decode_first_stage(samples.to(self.device))
+                log["mask"] = mask
+        if full and plot_progressive_rows:
+            with self.ema_scope("Plotting Progressives"):
+                _, progressives = self.progressive_denoising(
+                    c, shape=(self.channels, self.image_size, self.image_size), batch_size=N,
+                    start_T=getattr(self, "_progressive_start_T", None))
+            log["progressive_row"] = self._get_denoise_row_from_list(progressives, desc="Progressive Generation")
         if return_keys:
             return {k: v for k, v in log.items() if k in return_keys}
         return log

@@ -1343,6 +1343,60 @@ def ddim_step_indexed(x, e, noise, coef, index, x_prev, pred_x0=None, advance=Tr
                                         _p(x_prev), _p(pred_x0), _s()), "encdiff_ddim_step_indexed")
 
 
+def masked_renoise(img, x0, z, mask, t, sqrt_ac, sqrt_1mac):
+    """img = mask * (sqrt_ac[t] x0 + sqrt_1mac[t] z) + (1 - mask) * img, in place on img fp32 NCHW;
+    mask (B, 1, H, W) or (B, C, H, W); t device int64 [B]."""
+    B, Cc, H, W = img.shape
+    _f32c(img, img.shape, "img"), _f32c(x0, img.shape, "x0"), _f32c(z, img.shape, "z")
+    assert mask.dim() == 4 and mask.shape[0] == B and tuple(mask.shape[2:]) == (H, W), \
+        f"mask {tuple(mask.shape)} does not fit img {tuple(img.shape)}"
+    _f32c(mask, mask.shape, "mask")
+    assert t.dtype == torch.int64 and t.numel() == B
+    check(lib.encdiff_masked_renoise(_p(img), _p(x0), _p(z), _p(mask), mask.shape[1], _p(t), _p(sqrt_ac),
+                                     _p(sqrt_1mac), B, Cc, H * W, _s()), "encdiff_masked_renoise")
+
+
+def _sampler_args(x, e, noise, x_out, x0_out, coef, index, advance, codebook, idx_out, clamp=False):
+    B, Cc, H, W = x.shape
+    _f32c(x, x.shape, "x"), _f32c(e, x.shape, "e"), _f32c(x_out, x.shape, "x_out")
+    a = L.SamplerStepArgs(batch=B, c=Cc, hw=H * W, clamp=int(bool(clamp)), x=_p(x), e=_p(e), x_out=_p(x_out))
+    if noise is not None:
+        a.noise = _p(_f32c(noise, x.shape, "noise"))
+    if x0_out is not None:
+        a.x0_out = _p(_f32c(x0_out, x.shape, "x0_out"))
+    if index is not None:
+        assert index.dtype == torch.int32 and coef.dtype == F32 and coef.is_contiguous()
+        a.coef, a.index, a.advance = _p(coef), _p(index), int(bool(advance))
+    else:
+        a.coef_host = (C.c_float * 5)(*[float(v) for v in coef], *([0.0] * (5 - len(coef))))
+    if codebook is not None:
+        a.n_e = codebook.shape[0]
+        a.codebook = _p(_f32c(codebook, (a.n_e, codebook.shape[1]), "codebook"))
+        assert codebook.shape[1] == Cc, "the codebook's e_dim is the latent's channel count"
+        if idx_out is not None:
+            assert idx_out.dtype == torch.int32 and idx_out.is_contiguous() and idx_out.numel() == B * H * W
+            a.idx_out = _p(idx_out)
+    else:
+        assert idx_out is None, "indices need a codebook"
+    return a
+
+
+def ddim_step_quantized(x, e, noise, coef, codebook, x_prev, pred_x0=None, idx=None, index=None, advance=True):
+    """DDIM update with pred_x0 replaced by its nearest codebook entry (EncdiffSamplerStepArgs).
+    coef: (a_t, a_prev, sigma, sqrt(1 - a_t)) scalars, or with `index` (device int32) the device
+    table [S][4] of ddim_step_indexed.  idx: optional int32 [B*H*W] indices.  x_prev may be x."""
+    a = _sampler_args(x, e, noise, x_prev, pred_x0, coef, index, advance, codebook, idx)
+    check(lib.encdiff_ddim_step_quantized(C.byref(a), _s()), "encdiff_ddim_step_quantized")
+
+
+def ancestral_step(x, e, noise, coef, index, x_prev, x_recon=None, clamp=False, advance=True, codebook=None,
+                   idx=None):
+    """p_sample's update at t = *index (device int32) from the model's table coef [T][5]
+    (LatentDiffusion.ancestral_table); codebook: quantise x_recon.  x_prev may be x."""
+    a = _sampler_args(x, e, noise, x_prev, x_recon, coef, index, advance, codebook, idx, clamp=clamp)
+    check(lib.encdiff_ancestral_step(C.byref(a), _s()), "encdiff_ancestral_step")
+
+
 def adamw_ema(p, g, m, v, hyper, ema=None, ema_n=0, mirror=None):
     """mirror: bf16 buffer of p's size that receives the updated weights (arena.mirror)."""
     check(lib.encdiff_adamw_ema_mirror(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), _p(hyper), ema_n, _p(mirror),

@@ -890,6 +890,69 @@ typedef struct EncdiffVqArgs {
 
 int encdiff_vq_lookup(const EncdiffVqArgs* args, void* stream);
 
+/* ---------------------------------------------------------------- sampling steps
+ * The per-step updates of the sampling loops that log_images runs (ddpm_enc.py:1473-1596) beyond
+ * plain DDIM: inpainting, quantised x0 and the ancestral (p_sample) loop.  fp32 NCHW latents
+ * [batch][c][hw].  Timesteps and coefficient rows are read from device memory at execution time,
+ * so one captured step replays a whole loop.
+ */
+
+/* Masked re-noise, in place on img:
+ *   img = mask * (sqrt_ac[t] x0 + sqrt_1mac[t] z) + (1 - mask) * img
+ * (q_sample(x0, ts) * mask + (1. - mask) * img: ddim.py's sampling loop, ddpm_enc.py:1362-1365,
+ * 1411-1413).  t: device int64 [batch], as for encdiff_q_sample.  mask: fp32 [batch][mask_c][hw],
+ * mask_c == 1 (broadcast over the channels) or mask_c == c, else ENCDIFF_ERR_SHAPE.  Where
+ * mask == 0 img keeps its bits; where mask == 1 it receives encdiff_q_sample's value bitwise. */
+int encdiff_masked_renoise(float* img, const float* x0, const float* z, const float* mask, int mask_c,
+                           const long long* t, const float* sqrt_ac, const float* sqrt_1mac, int batch, int c,
+                           int hw, void* stream);
+
+/* One sampling step, shared by the two entry points below.
+ * Coefficients: the row coef[*index] of a device table (index a device int; `advance` != 0
+ * decrements *index after the update, as encdiff_ddim_step_indexed does), or, with index and coef
+ * NULL, the scalars coef_host (DDIM only).
+ * n_e > 0 quantises x0 before the update is finished: per pixel the nearest entry of
+ * codebook [n_e][c] to the pixel's x0 vector, by the search of encdiff_vq_lookup (direct fp32
+ * distance sum_ch (x0_ch - E_j,ch)^2, ties to the lowest index, a pixel with no finite distance
+ * takes entry 0).  x0_out receives the codebook entry itself and the update continues from it;
+ * the torch quantiser returns z + (z_q - z), which differs from the entry by at most one rounding
+ * of |z|.  Limits: c = e_dim <= 8 and n_e <= 8192, else ENCDIFF_ERR_SHAPE.
+ * x_out may alias x. */
+typedef struct EncdiffSamplerStepArgs {
+  int batch, c, hw;
+  int n_e;                    /* 0: no quantisation (codebook, idx_out NULL)                 */
+  int clamp;                  /* ancestral: clamp x_recon to [-1, 1] (before quantising)     */
+  int advance;                /* *index -= 1 after the update (needs index)                  */
+  float coef_host[5];         /* the coefficient row when index == NULL                      */
+  int pad_;
+  const float* x;             /* x_t                                                         */
+  const float* e;             /* the model's eps                                             */
+  const float* noise;         /* N(0, I) draw of x's shape; NULL: none added                 */
+  const float* coef;          /* device table [rows][4] (DDIM) / [rows][5] (ancestral)       */
+  int* index;                 /* device row index                                            */
+  const float* codebook;      /* fp32 [n_e][c]                                               */
+  float* x_out;               /* x_{t-1}                                                     */
+  float* x0_out;              /* optional: pred_x0 / x_recon (after clamp and quantisation)  */
+  int* idx_out;               /* optional, n_e > 0: int32 [batch*hw] codebook indices        */
+} EncdiffSamplerStepArgs;
+
+/* DDIM update with quantised pred_x0 (ddim.py p_sample_ddim, quantize_denoised branch):
+ *   pred_x0 = quantise((x - s1 e) / sqrt(a_t));
+ *   x' = sqrt(a_prev) pred_x0 + sqrt(1 - a_prev - sigma^2) e + sigma z
+ * with the row {a_t, a_prev, sigma, s1 = sqrt(1 - a_t)} of encdiff_ddim_step(_indexed).
+ * n_e > 0 and codebook are required. */
+int encdiff_ddim_step_quantized(const EncdiffSamplerStepArgs* args, void* stream);
+
+/* Ancestral step p_sample (ddpm_enc.py:234-247 predict_start_from_noise / q_posterior,
+ * 1255-1315 p_mean_variance / p_sample), row t = *index of a table [T][5] =
+ * {sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, posterior_mean_coef1,
+ *  posterior_mean_coef2, posterior_log_variance_clipped}:
+ *   x_recon = c0 x - c1 e; clamp to [-1, 1] if `clamp`; quantise if n_e > 0 (:1274-1277);
+ *   mean = m1 x_recon + m2 x;  x' = mean + (t != 0) exp(0.5 logvar) z.
+ * At t == 0 (and with noise NULL) nothing is added: x' is mean bitwise.  coef and index are
+ * required. */
+int encdiff_ancestral_step(const EncdiffSamplerStepArgs* args, void* stream);
+
 /* Library/device information (for tests): returns the number of exported kernels. */
 int encdiff_version(void);
 
