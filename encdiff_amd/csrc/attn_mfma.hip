@@ -971,7 +971,9 @@ int launch_mfma_fwd(const EncdiffAttnArgs& a, hipStream_t s) {
     constexpr int NT = fwd_tiles_per_task(DH);
     const int npairs = (((a.sq + 15) >> 4) + NT - 1) / NT;
     nqb = (npairs + 3) / 4;
-    lds = (size_t)2 * kch * DP * sizeof(bf16_t);
+    // + the key norms: a head of exactly kch padded keys (SKP == kch) still runs the resident
+    // branch of the kernel, which keeps kn behind its K / V
+    lds = (size_t)2 * kch * DP * sizeof(bf16_t) + 16 * sizeof(float);
   }
   // wide single-head blocks with few (image, head) workgroups (the VQ AttnBlock at 16x16: 128
   // workgroups of 128 KB K / V): query tasks spread over blockIdx.y, each workgroup staging the
