@@ -262,6 +262,7 @@ _PROTOS = {
     "encdiff_masked_renoise": [vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp],
     "encdiff_ddim_step_quantized": [C.POINTER(SamplerStepArgs), vp],
     "encdiff_ancestral_step": [C.POINTER(SamplerStepArgs), vp],
+    "encdiff_ddim_invert_step": [C.POINTER(SamplerStepArgs), vp],
     "encdiff_version": [],
 }
 

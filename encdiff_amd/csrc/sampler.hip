@@ -1,6 +1,6 @@
 // Per-step kernels of the sampling loops behind LatentDiffusion.log_images: the masked re-noise
-// of inpainting, the ancestral (p_sample) update, and the quantised-x0 forms of the DDIM and the
-// ancestral update.  fp32 NCHW latents; all of it is latency-bound at the sampling shapes
+// of inpainting, the ancestral (p_sample) update, the quantised-x0 forms of the DDIM and the
+// ancestral update, and the DDIM inversion step (DDIMSamplerAttn.next_step).  fp32 NCHW latents; all of it is latency-bound at the sampling shapes
 // (2 048 pixels at N = 8), so each is one launch per step that a captured step graph replays:
 // timesteps and coefficient rows are read from device memory at execution time.
 //
@@ -11,7 +11,7 @@
 
 namespace {
 
-enum { STEP_DDIM = 0, STEP_ANCESTRAL = 1 };
+enum { STEP_DDIM = 0, STEP_ANCESTRAL = 1, STEP_INVERT = 2 };
 
 __global__ void renoise_kernel(float* img, const float* x0, const float* z, const float* mask, const int mask_c,
                                const long long* t, const float* sa, const float* s1a, const int batch, const int c,
@@ -40,7 +40,7 @@ struct Coef {
 // coefficient row of this step: the device table at *index, or the scalars of the call
 template <int KIND>
 ED_DEV Coef load_coef(const EncdiffSamplerStepArgs& p, int& row) {
-  constexpr int N = KIND == STEP_DDIM ? 4 : 5;
+  constexpr int N = KIND == STEP_DDIM ? 4 : (KIND == STEP_INVERT ? 2 : 5);
   Coef k;
   row = p.index ? *p.index : -1;
 #pragma unroll
@@ -84,6 +84,19 @@ struct AncestralMath {
   }
 };
 
+// DDIM inversion (ddim.py:469-482 next_step), k = {a_t, a_next}: the deterministic step upwards in t
+struct InvertMath {
+  float s1, sa, san, dn;
+  ED_DEV InvertMath(const Coef& k, int) {
+    s1 = sqrtf(1.f - k.v[0]);
+    sa = sqrtf(k.v[0]);
+    san = sqrtf(k.v[1]);
+    dn = sqrtf(1.f - k.v[1]);
+  }
+  ED_DEV float x0(float x, float e, int) const { return (x - s1 * e) / sa; }
+  ED_DEV float next(float x0v, float, float e, const float*, long) const { return san * x0v + dn * e; }
+};
+
 template <int KIND>
 struct MathOf {
   typedef DdimMath type;
@@ -91,6 +104,10 @@ struct MathOf {
 template <>
 struct MathOf<STEP_ANCESTRAL> {
   typedef AncestralMath type;
+};
+template <>
+struct MathOf<STEP_INVERT> {
+  typedef InvertMath type;
 };
 
 template <int KIND>
@@ -144,6 +161,7 @@ __global__ __launch_bounds__(VQ_T) void step_quant_kernel(const EncdiffSamplerSt
 }
 
 __global__ void step_index_dec_kernel(int* index) { *index -= 1; }
+__global__ void step_index_inc_kernel(int* index) { *index += 1; }  // inversion walks upwards in t
 
 inline int grid_of(long n) {
   const long g = (n + 255) / 256;
@@ -163,13 +181,19 @@ void quant_launch(const EncdiffSamplerStepArgs& a, hipStream_t s) {
 template <int KIND>
 int step_launch(const EncdiffSamplerStepArgs* a, void* stream) {
   if (!a || !a->x || !a->e || !a->x_out) return ENCDIFF_ERR_ARG;
+  // inversion adds no noise and quantises nothing
+  if (KIND == STEP_INVERT && (a->noise || a->codebook || a->n_e != 0 || a->clamp || a->idx_out))
+    return ENCDIFF_ERR_ARG;
   if ((a->index != nullptr) != (a->coef != nullptr)) return ENCDIFF_ERR_ARG;
   if (KIND == STEP_ANCESTRAL && !a->index) return ENCDIFF_ERR_ARG;  // t is the table row
   if (a->advance && !a->index) return ENCDIFF_ERR_ARG;
   if (a->batch <= 0 || a->c <= 0 || a->hw <= 0) return ENCDIFF_ERR_SHAPE;
-  if ((long)a->batch * a->hw * VQ_MAX_DIM >= (1L << 31)) return ENCDIFF_ERR_SHAPE;
+  if (KIND != STEP_INVERT && (long)a->batch * a->hw * VQ_MAX_DIM >= (1L << 31)) return ENCDIFF_ERR_SHAPE;
   hipStream_t s = (hipStream_t)stream;
-  if (a->n_e != 0 || a->codebook) {
+  if constexpr (KIND == STEP_INVERT) {
+    if ((long)a->batch * a->c * a->hw >= (1L << 31)) return ENCDIFF_ERR_SHAPE;
+    hipLaunchKernelGGL(step_kernel<KIND>, dim3(grid_of((long)a->batch * a->c * a->hw)), dim3(256), 0, s, *a);
+  } else if (a->n_e != 0 || a->codebook) {
     if (a->c > VQ_MAX_DIM || a->n_e < 1 || a->n_e > VQ_MAX_CODES) return ENCDIFF_ERR_SHAPE;
     if (!a->codebook) return ENCDIFF_ERR_ARG;
     switch (a->c) {
@@ -189,7 +213,11 @@ int step_launch(const EncdiffSamplerStepArgs* a, void* stream) {
   }
   ED_CHECK_LAUNCH();
   if (a->advance) {
-    hipLaunchKernelGGL(step_index_dec_kernel, dim3(1), dim3(1), 0, s, a->index);
+    if (KIND == STEP_INVERT) {
+      hipLaunchKernelGGL(step_index_inc_kernel, dim3(1), dim3(1), 0, s, a->index);
+    } else {
+      hipLaunchKernelGGL(step_index_dec_kernel, dim3(1), dim3(1), 0, s, a->index);
+    }
     ED_CHECK_LAUNCH();
   }
   return ENCDIFF_OK;
@@ -216,4 +244,8 @@ extern "C" int encdiff_ddim_step_quantized(const EncdiffSamplerStepArgs* a, void
 
 extern "C" int encdiff_ancestral_step(const EncdiffSamplerStepArgs* a, void* stream) {
   return step_launch<STEP_ANCESTRAL>(a, stream);
+}
+
+extern "C" int encdiff_ddim_invert_step(const EncdiffSamplerStepArgs* a, void* stream) {
+  return step_launch<STEP_INVERT>(a, stream);
 }

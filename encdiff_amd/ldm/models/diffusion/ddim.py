@@ -32,6 +32,8 @@ and the final sample is not blended, as in the reference's loop.
 Before a replay the model's bf16 weight packs are refreshed if the parameters changed in
 place since the capture (LatentDiffusion.refresh_hip_weights): a sampler captured outside
 ema_scope() samples with the EMA weights inside it.
+
+DDIMSamplerAttn (ddim.py:210-482) adds DDIM inversion on the same switches: see its docstring.
 """
 from __future__ import annotations
 
@@ -457,3 +459,235 @@ class DDIMSampler(object):
             ops.ddim_step_indexed(st["x"], e_t.float().contiguous(), z, self._coef, idx, st["x2"], st["px0"],
                                   advance=True)
         st["x"].copy_(st["x2"])
+
+
+class DDIMSamplerAttn(DDIMSampler):
+    """Mirror of ldm/models/diffusion/ddim.py:210-482: DDIMSampler's sampling with the
+    ``return_context`` kwarg and the 'context' intermediates key, plus DDIM inversion
+    (ddim_inversion / ddim_loop / next_step): the deterministic (eta = 0) DDIM update walked
+    upwards in t, x_0 -> x_T, one UNet forward and one ops.ddim_invert_step launch per step.
+
+    ``return_context=True`` is refused: the reference's UNetModel.forward swallows the kwarg
+    (openaimodel_enc.py:712) and returns the eps tensor, so the reference's ``out[0]`` / ``out[1]``
+    are batch rows of eps, not (eps, context) -- there is no context to mirror.
+
+    The inversion loop runs on DDIMSampler's switches: eager (``use_graph=False``: host-scalar
+    coefficients), a one-step graph (timestep row, coefficient row {a_t, a_next} and step index
+    read on the device; the launch walks the index up; replayed S times) and, from the
+    LOOP_GRAPH_AFTER-th call of a shape on and up to GRAPH_MAX_STEPS steps, the whole loop as one
+    graph: step i reads slot i and writes slot i + 1 of a trajectory buffer (S + 1, B, C, H, W) of
+    the cache entry, K / V of the conditioning and the FiLM rows of the S ascending timesteps
+    computed once (HOIST).  Cache entries are keyed "inv_loop" / "inv_step", apart from the sampling
+    graphs' "loop" / "step".  Every returned latent is a clone."""
+
+    def __init__(self, model, schedule="linear", **kwargs):
+        super().__init__(model, schedule=schedule, **kwargs)
+        self._inv_tables = {}  # schedule key -> device table [S][2] = {a_t, a_next}, kept like _tables
+
+    def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0., verbose=True):
+        super().make_schedule(ddim_num_steps, ddim_discretize=ddim_discretize, ddim_eta=ddim_eta, verbose=verbose)
+        tab = self._inv_tables.get(self._sched_key)
+        if tab is None:
+            coef = np.stack([self.ddim_alphas, self.ddim_alphas_next], axis=1).astype(np.float32)
+            tab = self._inv_tables[self._sched_key] = torch.tensor(coef, device=self.model.device)
+        self._inv_coef = tab
+
+    @staticmethod
+    def _no_context(return_context):
+        if return_context:
+            raise NotImplementedError(
+                "return_context=True has nothing to mirror: the reference's UNetModel.forward swallows the "
+                "kwarg (openaimodel_enc.py:712) and returns the eps tensor, so out[0] / out[1] in its "
+                "DDIMSamplerAttn are batch rows of eps, not (eps, context)")
+
+    # ------------------------------------------------------------ sampling: DDIMSampler's paths
+    @torch.no_grad()
+    def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None,
+               img_callback=None, quantize_x0=False, eta=0., mask=None, x0=None, temperature=1.,
+               noise_dropout=0., score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None,
+               log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None,
+               return_context=False, mask_normals_sequence=None, **kwargs):
+        self._no_context(return_context)
+        return super().sample(S, batch_size, shape, conditioning=conditioning, callback=callback,
+                              normals_sequence=normals_sequence, img_callback=img_callback, quantize_x0=quantize_x0,
+                              eta=eta, mask=mask, x0=x0, temperature=temperature, noise_dropout=noise_dropout,
+                              score_corrector=score_corrector, corrector_kwargs=corrector_kwargs, verbose=verbose,
+                              x_T=x_T, log_every_t=log_every_t,
+                              unconditional_guidance_scale=unconditional_guidance_scale,
+                              unconditional_conditioning=unconditional_conditioning,
+                              mask_normals_sequence=mask_normals_sequence, **kwargs)
+
+    @torch.no_grad()
+    def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
+                      quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100,
+                      temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
+                      unconditional_guidance_scale=1., unconditional_conditioning=None, return_context=False,
+                      normals_sequence=None, mask_normals_sequence=None):
+        self._no_context(return_context)
+        img, intermediates = super().ddim_sampling(
+            cond, shape, x_T=x_T, ddim_use_original_steps=ddim_use_original_steps, callback=callback,
+            timesteps=timesteps, quantize_denoised=quantize_denoised, mask=mask, x0=x0, img_callback=img_callback,
+            log_every_t=log_every_t, temperature=temperature, noise_dropout=noise_dropout,
+            score_corrector=score_corrector, corrector_kwargs=corrector_kwargs,
+            unconditional_guidance_scale=unconditional_guidance_scale,
+            unconditional_conditioning=unconditional_conditioning, normals_sequence=normals_sequence,
+            mask_normals_sequence=mask_normals_sequence)
+        intermediates["context"] = []
+        return img, intermediates
+
+    @torch.no_grad()
+    def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
+                      temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
+                      unconditional_guidance_scale=1., unconditional_conditioning=None, return_context=False,
+                      noise=None):
+        self._no_context(return_context)
+        return super().p_sample_ddim(x, c, t, index, repeat_noise=repeat_noise, use_original_steps=use_original_steps,
+                                     quantize_denoised=quantize_denoised, temperature=temperature,
+                                     noise_dropout=noise_dropout, score_corrector=score_corrector,
+                                     corrector_kwargs=corrector_kwargs,
+                                     unconditional_guidance_scale=unconditional_guidance_scale,
+                                     unconditional_conditioning=unconditional_conditioning, noise=noise)
+
+    # ------------------------------------------------------------ inversion
+    @torch.no_grad()
+    def ddim_inversion(self, latent, cond, timesteps, ddim_use_original_steps=False, return_context=False):
+        ddim_latents, intermediates = self.ddim_loop(latent, cond, timesteps, ddim_use_original_steps, return_context)
+        return ddim_latents[-1], intermediates
+
+    @torch.no_grad()
+    def ddim_loop(self, latent, cond, timesteps, ddim_use_original_steps=False, return_context=False):
+        """ddim.py:434-467: S = ``timesteps`` inversion steps in ascending order of ddim_timesteps;
+        loop step i evaluates the model at t = ddim_timesteps[i] and applies next_step with
+        a_t = ddim_alphas[i], a_next = ddim_alphas_next[i].  Returns (all_latent, {"context": []}),
+        all_latent = [latent itself, then the S latents after each step]."""
+        self._no_context(return_context)
+        if ddim_use_original_steps:
+            raise NotImplementedError("ddim_use_original_steps is not used by EncDiff")
+        all_latent = [latent]
+        self.make_schedule(ddim_num_steps=timesteps, ddim_eta=0., verbose=False)
+        steps = self.ddim_timesteps
+        total = steps.shape[0]
+        intermediates = {"context": []}
+        x = latent.clone().detach()
+        if self.use_graph and x.is_cuda and isinstance(cond, torch.Tensor):
+            x = x.float().contiguous()
+            if total <= GRAPH_MAX_STEPS:
+                lk = ("inv", tuple(x.shape), total, self._sched_key, tuple(cond.shape), cond.dtype)
+                seen = self._seen.get(lk, 0)
+                self._seen[lk] = seen + 1
+                if seen >= LOOP_GRAPH_AFTER:
+                    return all_latent + self._inv_loop_graph(cond, x, total), intermediates
+            return all_latent + self._inv_step_graph(cond, x, total), intermediates
+        b = x.shape[0]
+        for i, step in enumerate(steps):
+            ts = torch.full((b,), int(step), device=x.device, dtype=torch.long)
+            e_t = self.model.apply_model(x, ts, cond)
+            if x.is_cuda:
+                x = x.float().contiguous()
+                x_next = torch.empty_like(x)
+                ops.ddim_invert_step(x, e_t.float().contiguous(), self._inv_row(i), x_next)
+                x = x_next
+            else:
+                x = self.next_step(e_t, i, x, ddim_use_original_steps)
+            all_latent.append(x)
+        return all_latent, intermediates
+
+    def next_step(self, model_output, index, sample, use_original_steps):
+        """ddim.py:469-482, the reference's torch expression (any device; the captured and the eager
+        HIP loops run ops.ddim_invert_step instead)."""
+        b, device = model_output.shape[0], model_output.device
+        alphas = self.model.alphas_cumprod if use_original_steps else self.ddim_alphas
+        alphas_next = self.model.alphas_cumprod_next if use_original_steps else self.ddim_alphas_next
+        a_t = torch.full((b, 1, 1, 1), float(alphas[index]), device=device)
+        a_next = torch.full((b, 1, 1, 1), float(alphas_next[index]), device=device)
+        b_t = 1 - a_t
+        next_original_sample = (sample - b_t ** 0.5 * model_output) / a_t ** 0.5
+        next_sample_direction = (1 - a_next) ** 0.5 * model_output
+        return a_next ** 0.5 * next_original_sample + next_sample_direction
+
+    def _inv_row(self, i):
+        return float(self.ddim_alphas[i]), float(self.ddim_alphas_next[i])
+
+    def _inv_entry(self, kind, cond, x, total):
+        key = (kind, tuple(x.shape), total, self._sched_key, tuple(cond.shape), cond.dtype)
+        st = self._graphs.get(key)
+        if st is None:
+            # slot 0: the caller's latent; the one-step graph updates slot 0 in place
+            slots = total + 1 if kind == "inv_loop" else 1
+            st = self._graphs[key] = dict(key=key, traj=torch.empty(slots, *x.shape, device=x.device),
+                                          cond=torch.empty_like(cond), graph=None)
+        st["cond"].copy_(cond)
+        st["traj"][0].copy_(x)
+        return st
+
+    def _capture(self, body):
+        g = torch.cuda.CUDAGraph()
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
+                body()
+        torch.cuda.current_stream().wait_stream(s)
+        return g
+
+    def _inv_loop_graph(self, cond, x, total):
+        """The whole inversion loop as one HIP graph: step i reads slot i and writes slot i + 1 of
+        the entry's trajectory buffer (no copy nodes); coefficients are kernel arguments."""
+        st = self._inv_entry("inv_loop", cond, x, total)
+        self._refresh()
+        if st["graph"] is None:
+            ts = np.asarray(self.ddim_timesteps, dtype=np.int64)
+            st["ts"] = torch.tensor(np.repeat(ts[:, None], x.shape[0], axis=1), device=x.device)
+            st["ts_col"] = st["ts"][:, 0].contiguous()  # ascending: the FiLM table of the loop
+            self._inv_loop_body(st, total)  # warm-up (slot 0 is only read)
+            st["graph"] = self._capture(lambda: self._inv_loop_body(st, total))
+        st["graph"].replay()
+        return [st["traj"][k].clone() for k in range(1, total + 1)]
+
+    def _inv_loop_body(self, st, total):
+        ex = self._hip_executor() if HOIST else None
+        if ex is not None:
+            ex.samp_ts, ex.samp_i = st["ts_col"], None
+        um = self._borrow(True)
+        traj = st["traj"]
+        try:
+            for i in range(total):
+                if ex is not None:
+                    ex.samp_i = i
+                e_t = self.model.apply_model(traj[i], st["ts"][i], st["cond"])
+                ops.ddim_invert_step(traj[i], e_t.float().contiguous(), self._inv_row(i), traj[i + 1])
+        finally:
+            if ex is not None:
+                ex.samp_ts = ex.samp_i = None
+            if um is not None:
+                um.borrow_eps = False
+
+    def _inv_step_graph(self, cond, x, total):
+        """One captured inversion step (timestep and coefficient row looked up at a device step
+        index that the launch walks up), replayed S times."""
+        st = self._inv_entry("inv_step", cond, x, total)
+        self._refresh()
+        if st["graph"] is None:
+            dev = x.device
+            st.update(t=torch.empty(x.shape[0], device=dev, dtype=torch.long),
+                      idx=torch.zeros(1, device=dev, dtype=torch.int32))
+            self._inv_step_body(st)  # warm-up at row 0
+            st["traj"][0].copy_(x)
+            st["graph"] = self._capture(lambda: self._inv_step_body(st))
+        st["idx"].zero_()
+        out = []
+        for _ in range(total):
+            st["graph"].replay()
+            out.append(st["traj"][0].clone())
+        return out
+
+    def _inv_step_body(self, st):
+        x, idx = st["traj"][0], st["idx"]
+        st["t"].copy_(self._ts.index_select(0, idx.long()).expand(st["t"].shape[0]))
+        um = self._borrow(True)
+        try:
+            e_t = self.model.apply_model(x, st["t"], st["cond"])
+        finally:
+            if um is not None:
+                um.borrow_eps = False
+        ops.ddim_invert_step(x, e_t.float().contiguous(), self._inv_coef, x, index=idx, advance=True)

@@ -32,7 +32,7 @@ from ...util import count_params, default, exists, instantiate_from_config
 from ...modules.diffusionmodules.util import extract_into_tensor, make_beta_schedule
 from ...modules.ema import LitEma
 from ..autoencoder import IdentityFirstStage, VQModelInterface
-from .ddim import DDIMSampler
+from .ddim import DDIMSampler, DDIMSamplerAttn
 
 __conditioning_keys__ = {"concat": "c_concat", "crossattn": "c_crossattn", "adm": "y"}
 
@@ -352,6 +352,9 @@ class LatentDiffusion(DDPM):
     # log_images also runs the reference's quantised-x0, inpainting / outpainting, denoise and
     # progressive rows (ENCDIFF_LOG_IMAGES_FULL=1 sets it in setup_hip_training)
     log_images_full = False
+    # log_images also logs the DDIM-inversion rows inversion_reconstruction and samples_swap_inverted
+    # (ENCDIFF_LOG_IMAGES_INVERSION=1 sets it in setup_hip_training)
+    log_images_inversion = False
     # the ancestral loops replay one captured step where nothing needs the host between steps
     # (False: always launch the kernels step by step)
     ancestral_use_graph = True
@@ -569,6 +572,8 @@ class LatentDiffusion(DDPM):
             self._ema_fused = True
         if os.environ.get("ENCDIFF_LOG_IMAGES_FULL", "0") == "1":
             self.log_images_full = True
+        if os.environ.get("ENCDIFF_LOG_IMAGES_INVERSION", "0") == "1":
+            self.log_images_inversion = True
         self._arena = arena
         return arena
 
@@ -600,6 +605,14 @@ class LatentDiffusion(DDPM):
             s = self._ddim_sampler = DDIMSampler(self)
         return s
 
+    def ddim_attn_sampler(self):
+        """One DDIMSamplerAttn per model, cached like ddim_sampler(): its captured inversion (and
+        sampling) graphs are reused by every later sample_log_attn / log_images call."""
+        s = getattr(self, "_ddim_attn_sampler", None)
+        if s is None:
+            s = self._ddim_attn_sampler = DDIMSamplerAttn(self)
+        return s
+
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, **kwargs):
         if not ddim:
@@ -607,6 +620,17 @@ class LatentDiffusion(DDPM):
         sampler = self.ddim_sampler()
         shape = (self.channels, self.image_size, self.image_size)
         return sampler.sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
+
+    @torch.no_grad()
+    def sample_log_attn(self, cond, batch_size, ddim, ddim_steps, return_context=False, **kwargs):
+        """ddpm_enc.py:1457-1470."""
+        if not ddim:
+            return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True,
+                               return_context=return_context, **kwargs)
+        sampler = self.ddim_attn_sampler()
+        shape = (self.channels, self.image_size, self.image_size)
+        return sampler.sample(ddim_steps, batch_size, shape, cond, verbose=False, return_context=return_context,
+                              **kwargs)
 
     @torch.no_grad()
     def sample_swap(self, orc, N, ddim_steps=200, eta=1., x_T=None, normals_sequence=None):
@@ -1025,6 +1049,18 @@ class LatentDiffusion(DDPM):
                                                      ddim_steps=ddim_steps, x0=z[:N], mask=mask)
                     log[name] = self.decode_first_stage(samples.to(self.device))
                 log["mask"] = mask
+        if self.log_images_inversion and use_ddim:
+            # encode -> invert under the image's own concept tokens -> re-sample (eta = 0) from x_T
+            shape = (self.channels, self.image_size, self.image_size)
+            with self.ema_scope("Plotting Inversion"):
+                z_T, _ = self.ddim_attn_sampler().ddim_inversion(z[:N], c[:N], ddim_steps)
+                samples, _ = self.ddim_sampler().sample(ddim_steps, N, shape, c[:N], eta=0., verbose=False, x_T=z_T)
+            log["inversion_reconstruction"] = self.decode_first_stage(samples)
+            if sample_swap:
+                lu = self.model.diffusion_model.latent_unit
+                with self.ema_scope("Plotting Swapping Inverted"):
+                    log["samples_swap_inverted"] = self.decode_first_stage(
+                        self.sample_swap(orc, N, ddim_steps=ddim_steps, eta=0., x_T=z_T.repeat(lu, 1, 1, 1)))
         if full and plot_progressive_rows:
             with self.ema_scope("Plotting Progressives"):
                 _, progressives = self.progressive_denoising(

@@ -1397,6 +1397,15 @@ def ancestral_step(x, e, noise, coef, index, x_prev, x_recon=None, clamp=False, 
     check(lib.encdiff_ancestral_step(C.byref(a), _s()), "encdiff_ancestral_step")
 
 
+def ddim_invert_step(x, e, coef, x_next, pred_x0=None, index=None, advance=True):
+    """DDIM inversion step (DDIMSamplerAttn.next_step): x_next = sqrt(a_next) x0 + sqrt(1 - a_next) e
+    with x0 = (x - sqrt(1 - a_t) e) / sqrt(a_t).  coef: (a_t, a_next) scalars, or with `index`
+    (device int32) a device table [S][2]; advance: *index += 1 after the update (upwards in t, the
+    opposite of the sampling steps; ignored with scalars).  x_next may be x."""
+    a = _sampler_args(x, e, None, x_next, pred_x0, coef, index, advance, None, None)
+    check(lib.encdiff_ddim_invert_step(C.byref(a), _s()), "encdiff_ddim_invert_step")
+
+
 def adamw_ema(p, g, m, v, hyper, ema=None, ema_n=0, mirror=None):
     """mirror: bf16 buffer of p's size that receives the updated weights (arena.mirror)."""
     check(lib.encdiff_adamw_ema_mirror(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), _p(hyper), ema_n, _p(mirror),

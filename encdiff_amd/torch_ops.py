@@ -9,6 +9,7 @@ with aten ops:
   encdiff::q_sample       DDPM.q_sample                 (ddpm_enc.py:292-295)
   encdiff::l1_loss        LatentDiffusion.p_losses      (ddpm_enc.py:1194-1213): (loss, loss_vlb) + seed
   encdiff::ddim_step      DDIMSampler.p_sample_ddim     (ddim.py:188-207)
+  encdiff::ddim_invert_step  DDIMSamplerAttn.next_step  (ddim.py:469-482)
   encdiff::attention_fwd  CrossAttention core           (attention.py:170-193): (o, lse)
   encdiff::attention_bwd  its backward                  (dq, dk, dv)
 
@@ -76,6 +77,21 @@ def ddim_step(x: Tensor, e: Tensor, noise: Tensor, a_t: float, a_prev: float, si
 
 @ddim_step.register_fake
 def _(x, e, noise, a_t, a_prev, sigma, sqrt_one_minus_at):
+    return torch.empty_like(x, dtype=torch.float32), torch.empty_like(x, dtype=torch.float32)
+
+
+@custom_op("encdiff::ddim_invert_step", mutates_args=())
+def ddim_invert_step(x: Tensor, e: Tensor, a_t: float, a_next: float) -> Tuple[Tensor, Tensor]:
+    """-> (x_next, pred_x0)."""
+    _dev(x, e)
+    x = x.float().contiguous()
+    xn, px0 = torch.empty_like(x), torch.empty_like(x)
+    ops.ddim_invert_step(x, e.float().contiguous(), (a_t, a_next), xn, px0)
+    return xn, px0
+
+
+@ddim_invert_step.register_fake
+def _(x, e, a_t, a_next):
     return torch.empty_like(x, dtype=torch.float32), torch.empty_like(x, dtype=torch.float32)
 
 

@@ -922,13 +922,13 @@ typedef struct EncdiffSamplerStepArgs {
   int batch, c, hw;
   int n_e;                    /* 0: no quantisation (codebook, idx_out NULL)                 */
   int clamp;                  /* ancestral: clamp x_recon to [-1, 1] (before quantising)     */
-  int advance;                /* *index -= 1 after the update (needs index)                  */
+  int advance;                /* *index -= 1 (inversion: += 1) after the update (needs index) */
   float coef_host[5];         /* the coefficient row when index == NULL                      */
   int pad_;
   const float* x;             /* x_t                                                         */
   const float* e;             /* the model's eps                                             */
   const float* noise;         /* N(0, I) draw of x's shape; NULL: none added                 */
-  const float* coef;          /* device table [rows][4] (DDIM) / [rows][5] (ancestral)       */
+  const float* coef;          /* device table [rows][4] (DDIM) / [5] (ancestral) / [2] (inversion) */
   int* index;                 /* device row index                                            */
   const float* codebook;      /* fp32 [n_e][c]                                               */
   float* x_out;               /* x_{t-1}                                                     */
@@ -952,6 +952,26 @@ int encdiff_ddim_step_quantized(const EncdiffSamplerStepArgs* args, void* stream
  * At t == 0 (and with noise NULL) nothing is added: x' is mean bitwise.  coef and index are
  * required. */
 int encdiff_ancestral_step(const EncdiffSamplerStepArgs* args, void* stream);
+
+/* DDIM inversion step (ddim.py:469-482, DDIMSamplerAttn.next_step): the deterministic DDIM update
+ * walked upwards in t, x_t -> x_{t_next}.  Per element of the fp32 NCHW latent [batch][c][hw], with
+ * the coefficient row {a_t, a_next} (two fp32 values; all square roots are taken on the device in
+ * fp32 from these two):
+ *   x0    = (x - sqrt(1 - a_t) * e) / sqrt(a_t)
+ *   x_out = sqrt(a_next) * x0 + sqrt(1 - a_next) * e
+ * Coefficients: with index and coef NULL the scalars coef_host[0..1]; else the row
+ * coef[2 * *index .. 2 * *index + 1] of a device table [rows][2] (index a device int).
+ * Index direction: `advance` != 0 does *index += 1 after the update -- the inversion loop visits
+ * its table rows upwards, the OPPOSITE of encdiff_ddim_step_quantized / encdiff_ancestral_step /
+ * encdiff_ddim_step_indexed, which decrement.  advance == 0 leaves *index as it is.
+ * x0_out is optional (NULL: not written) and receives x0.  x_out receives the update and may alias
+ * x (every element is read before it is written, by the same thread).
+ * Refusals, nothing is launched and no output is touched:
+ *   x, e or x_out NULL; noise, codebook or idx_out non-NULL, n_e != 0 or clamp != 0 (inversion adds
+ *   no noise and quantises nothing); index without coef or coef without index; advance != 0 without
+ *   index: ENCDIFF_ERR_ARG.
+ *   batch, c or hw <= 0, or batch * c * hw >= 2^31: ENCDIFF_ERR_SHAPE. */
+int encdiff_ddim_invert_step(const EncdiffSamplerStepArgs* args, void* stream);
 
 /* Library/device information (for tests): returns the number of exported kernels. */
 int encdiff_version(void);

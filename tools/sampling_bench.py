@@ -10,6 +10,10 @@ recipe of tools/README.md:
     quantised    DDIM with quantize_x0, B = 8, S = 200, eta = 1: steps/s
     progressive  progressive_denoising at N = 8, T = 1000: seconds
     log_images   log_images(N = 8) with log_images_full: seconds
+    inversion    DDIM inversion (DDIMSamplerAttn.ddim_loop), B = 8, S = 200: steps/s of three arms timed
+                 in turn in the same process -- the captured inversion, plain DDIM sampling at eta = 0
+                 (the comparison: the same UNet plus one small launch per step) and the eager inversion
+                 loop (use_graph=False)
 
 It only calls the public API, so it also runs on a commit from before the captured masked /
 quantised paths (where these loops are the eager Python loop); what a commit does not have is
@@ -30,9 +34,39 @@ sys.path.insert(0, REPO)
 import torch  # noqa: E402
 
 
+def inversion_arms(ldm, steps, B, shape, cond, x0):
+    """{arm: callable} of the inversion workload (None on a commit without DDIMSamplerAttn)."""
+    from encdiff_amd.ldm.models.diffusion import ddim as D
+    if not hasattr(D, "DDIMSamplerAttn"):
+        return None
+    inv, plain = ldm.ddim_attn_sampler(), ldm.ddim_sampler()
+    eager = D.DDIMSamplerAttn(ldm, use_graph=False)
+    return {"inversion": lambda: inv.ddim_loop(x0, cond, steps),
+            "ddim_eta0": lambda: plain.sample(steps, B, shape, cond, eta=0.0, verbose=False, x_T=x0),
+            "inversion_eager": lambda: eager.ddim_loop(x0, cond, steps)}
+
+
+def time_arms(arms, a, res):
+    """Every round runs each arm once, in turn; the first --warm rounds are not timed."""
+    times = {k: [] for k in arms}
+    with torch.no_grad():
+        for i in range(a.warm + a.reps):
+            for k, fn in arms.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if i >= a.warm:
+                    times[k].append(time.perf_counter() - t0)
+    for k, t in times.items():
+        rate = [a.steps / v for v in t]
+        res[k] = {"seconds": t, "steps_per_s": rate, "steps_per_s_median": statistics.median(rate),
+                  "steps_per_s_min": min(rate), "steps_per_s_max": max(rate)}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", required=True, choices=["masked", "quantised", "progressive", "log_images"])
+    ap.add_argument("--what", required=True, choices=["masked", "quantised", "progressive", "log_images", "inversion"])
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--timesteps", type=int, default=1000, help="progressive: start_T")
@@ -71,13 +105,22 @@ def main():
             fn = lambda: ldm.progressive_denoising(cond, shape=shape, batch_size=B, verbose=False,  # noqa: E731
                                                    start_T=a.timesteps)
         res["timesteps"] = a.timesteps
+    elif a.what == "inversion":
+        res["steps"] = a.steps
+        arms = inversion_arms(ldm, a.steps, B, shape, cond, x0)
+        if arms is not None:
+            time_arms(arms, a, res)
+            res["graphs"] = sorted({k[0] for k in ldm.ddim_attn_sampler()._graphs} |
+                                   {k[0] for k in ldm.ddim_sampler()._graphs})
     else:
         if hasattr(type(ldm), "log_images_full"):
             ldm.log_images_full = True
             fn = lambda: ldm.log_images({"image": img}, N=B, ddim_steps=a.steps)  # noqa: E731
         res["steps"] = a.steps
 
-    if fn is None:
+    if a.what == "inversion" and "inversion" in res:
+        pass  # the three arms are in res
+    elif fn is None:
         res["seconds_median"] = "n/a"
     else:
         times = []
