@@ -12,14 +12,17 @@ lives in buffers owned by its cache entry (x_T, the conditioning, the per-step n
 the timestep rows), so a later call with other inputs copies them in and replays; the
 schedule coefficients are kernel arguments of the unrolled steps.  Loops longer than
 ``GRAPH_MAX_STEPS`` capture one step (coefficients and timestep looked up at a device step
-index) and replay it S times.
+index) and replay it S times.  The capture, the UNet's scope inside a loop (eps borrow, hoisted
+K / V and FiLM rows), the noise sources and the loop / step choice come from
+encdiff_amd/graph_loops.py; this file keeps the cache entries and the order of each loop's nodes.
 
 Noise: with eta > 0 each captured step draws its N(0, I) row inside the graph (torch's
 graph-safe Philox stream advances on every replay), so a loop holds one step's noise, not an
 (S, *x.shape) table.  ``normals_sequence`` (the reference's kwarg, unused there) injects a
 given table instead -- step i (in loop order, i = 0 .. S-1) adds sigma_i * normals_sequence[i]
 -- which is how the eta > 0 trajectory is pinned against the reference's CPU noise stream.
-At eta == 0 sigma is 0 for every step and no noise is drawn.
+At eta == 0 sigma is 0 for every step and no noise is drawn.  Either way the step noise is the
+entry's graph_loops.NoiseRows ``z`` (the inpainting re-noise: ``mz``).
 
 Inpainting (``mask`` + ``x0``) and ``quantize_x0`` run on the same captured paths: a masked step
 re-noises the known region in front of the UNet (ops.masked_renoise, its N(0, I) row drawn inside
@@ -43,6 +46,8 @@ import numpy as np
 import torch
 
 from encdiff_amd import ops, torch_ops  # noqa: F401  (torch_ops registers torch.ops.encdiff.*)
+from encdiff_amd.graph_loops import (NoiseRows, capture, kernel_mask, loop_or_step, noise_table, unet_loop,
+                                     vq_codebook)
 from ...modules.diffusionmodules.util import make_ddim_sampling_parameters, make_ddim_timesteps, noise_like
 
 GRAPH_MAX_STEPS = 256  # longer loops replay a one-step graph (device step index)
@@ -136,31 +141,27 @@ class DDIMSampler(object):
             steps = self.ddim_timesteps
         total = steps.shape[0]
         if normals_sequence is not None:
-            normals_sequence = self._noise_table(normals_sequence, total, img.shape, device)
+            normals_sequence = noise_table(normals_sequence, total, img.shape, device)
         if mask_normals_sequence is not None:
-            mask_normals_sequence = self._noise_table(mask_normals_sequence, total, img.shape, device,
-                                                      "mask_normals_sequence")
+            mask_normals_sequence = noise_table(mask_normals_sequence, total, img.shape, device,
+                                                "mask_normals_sequence")
         intermediates = {"x_inter": [img], "pred_x0": [img]}
         kmask = None  # the mask in the re-noise kernel's layout, (B, 1, H, W) or (B, C, H, W)
         if mask is not None:
             assert x0 is not None, "inpainting needs x0 with the mask"
-            kmask = self._kernel_mask(mask, img)
+            kmask = kernel_mask(mask, img)
         simple = (callback is None and img_callback is None and (mask is None or kmask is not None) and
-                  (not quantize_denoised or self._codebook(img) is not None) and
+                  (not quantize_denoised or vq_codebook(self.model, img) is not None) and
                   noise_dropout == 0. and score_corrector is None and temperature == 1. and
                   (unconditional_conditioning is None or unconditional_guidance_scale == 1.))
         if self.use_graph and simple and img.is_cuda and timesteps is None and isinstance(cond, torch.Tensor):
             extra = dict(mask=kmask, x0=x0, quant=bool(quantize_denoised), mask_normals=mask_normals_sequence)
-            if total <= GRAPH_MAX_STEPS:
-                lk = (tuple(img.shape), total, self._sched_key, tuple(cond.shape), cond.dtype, log_every_t,
-                      bool(normals_sequence is not None and self.ddim_eta),
-                      None if kmask is None else (tuple(kmask.shape), mask_normals_sequence is not None),
-                      bool(quantize_denoised))
-                seen = self._seen.get(lk, 0)
-                self._seen[lk] = seen + 1
-                if seen >= LOOP_GRAPH_AFTER:
-                    return self._loop_graph(cond, img, total, log_every_t, intermediates, normals_sequence, **extra)
-            return self._step_graph(cond, img, total, log_every_t, intermediates, normals_sequence, **extra)
+            lk = (tuple(img.shape), total, self._sched_key, tuple(cond.shape), cond.dtype, log_every_t,
+                  bool(normals_sequence is not None and self.ddim_eta),
+                  None if kmask is None else (tuple(kmask.shape), mask_normals_sequence is not None),
+                  bool(quantize_denoised))
+            run = self._loop_graph if self._path(lk, total) == "loop" else self._step_graph
+            return run(cond, img, total, log_every_t, intermediates, normals_sequence, **extra)
         for i, step in enumerate(np.flip(steps)):
             index = total - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
@@ -188,36 +189,6 @@ class DDIMSampler(object):
                 intermediates["pred_x0"].append(pred_x0)
         return img, intermediates
 
-    @staticmethod
-    def _noise_table(seq, total, shape, device, what="normals_sequence"):
-        t = torch.stack(list(seq)) if not isinstance(seq, torch.Tensor) else seq
-        t = t.to(device=device, dtype=torch.float32).contiguous()
-        if t.shape[0] < total or tuple(t.shape[1:]) != tuple(shape):
-            raise ValueError(f"{what} must hold {total} draws of shape {tuple(shape)}, got {tuple(t.shape)}")
-        return t
-
-    @staticmethod
-    def _kernel_mask(mask, img):
-        """mask as fp32 (B, 1, H, W) or (B, C, H, W) on img's device; None: another broadcast shape
-        (the torch expression of the eager loop handles it)."""
-        if not isinstance(mask, torch.Tensor) or mask.dim() != 4:
-            return None
-        B, C, H, W = img.shape
-        if tuple(mask.shape) not in ((B, 1, H, W), (B, C, H, W)):
-            return None
-        return mask.to(device=img.device, dtype=torch.float32).contiguous()
-
-    def _codebook(self, img):
-        """The first stage's codebook [n_e][e_dim] when the quantised-x0 kernel covers it (a VQ
-        first stage, e_dim == the latent's channels, within the kernel's limits), else None."""
-        q = getattr(getattr(self.model, "first_stage_model", None), "quantize", None)
-        w = getattr(getattr(q, "embedding", None), "weight", None)
-        if w is None or not img.is_cuda or w.dim() != 2 or w.shape[1] != img.shape[1]:
-            return None
-        if not ops.vq_supported(w.shape[0], w.shape[1]) or w.dtype != torch.float32 or not w.is_contiguous():
-            return None
-        return w.detach()
-
     @torch.no_grad()
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
@@ -241,7 +212,7 @@ class DDIMSampler(object):
             noise = torch.nn.functional.dropout(noise, p=noise_dropout)
         x = x.float().contiguous()
         e_t = e_t.float().contiguous()
-        cb = self._codebook(x) if quantize_denoised else None
+        cb = vq_codebook(self.model, x) if quantize_denoised else None
         if cb is not None:
             x_prev, pred_x0 = torch.empty_like(x), torch.empty_like(x)
             ops.ddim_step_quantized(x, e_t, noise.float().contiguous(), (a_t, a_prev, sigma, s1), cb, x_prev, pred_x0)
@@ -254,13 +225,17 @@ class DDIMSampler(object):
         return torch.ops.encdiff.ddim_step(x, e_t, noise, a_t, a_prev, sigma, s1)
 
     # ------------------------------------------------------------ captured loops
-    def _entry(self, kind, cond, img, total, log_every_t, injected, mask=None, x0=None, quant=False,
+    def _path(self, key, total):
+        """"loop" or "step" for this call of the loop ``key`` (graph_loops.loop_or_step)."""
+        return loop_or_step(self._seen, key, total, LOOP_GRAPH_AFTER, GRAPH_MAX_STEPS)
+
+    def _entry(self, kind, cond, img, total, log_every_t, normals, mask=None, x0=None, quant=False,
                mask_normals=None):
-        """Cache entry (static input / output buffers) of a captured loop.  ``injected``: the
-        noise comes from a caller's normals_sequence table (else drawn inside the graph).  mask /
-        x0: inpainting (buffers of the entry, copied in per call; mask_normals: the re-noise table
-        is injected too); quant: pred_x0 is quantised."""
-        injected = bool(injected and self.ddim_eta)
+        """Cache entry (static input / output buffers) of a captured loop.  normals: the caller's
+        normals_sequence table (None: the noise is drawn inside the graph).  mask / x0: inpainting
+        (buffers of the entry, copied in per call; mask_normals: the re-noise table is injected
+        too); quant: pred_x0 is quantised."""
+        injected = bool(normals is not None and self.ddim_eta)
         mkey = None if mask is None else (tuple(mask.shape), mask_normals is not None)
         key = (kind, tuple(img.shape), total, self._sched_key, tuple(cond.shape), cond.dtype, log_every_t,
                injected, mkey, bool(quant))
@@ -272,25 +247,20 @@ class DDIMSampler(object):
                       cond=torch.empty_like(cond), logs=logs,
                       log_x=torch.empty(len(logs), *img.shape, device=dev),
                       log_px0=torch.empty(len(logs), *img.shape, device=dev),
-                      noise=torch.zeros((total if injected else 1), *img.shape, device=dev),
-                      draw=bool(self.ddim_eta) and not injected, graph=None, mask=None,
-                      codebook=self._codebook(img) if quant else None)
+                      z=NoiseRows(total, img.shape, dev, injected, draw=bool(self.ddim_eta)), graph=None, mask=None,
+                      codebook=vq_codebook(self.model, img) if quant else None)
             if mask is not None:
-                st.update(mask=torch.empty_like(mask), x0=torch.empty_like(img), mdraw=mask_normals is None,
-                          mnoise=torch.zeros((1 if mask_normals is None else total), *img.shape, device=dev))
+                st.update(mask=torch.empty_like(mask), x0=torch.empty_like(img),
+                          mz=NoiseRows(total, img.shape, dev, mask_normals is not None))
             self._graphs[key] = st
         st["cond"].copy_(cond)
         st["x"].copy_(img)
+        st["z"].fill(normals)
         if mask is not None:
             st["mask"].copy_(mask)
             st["x0"].copy_(x0)
-            if mask_normals is not None:
-                st["mnoise"].copy_(mask_normals[:total])
+            st["mz"].fill(mask_normals)
         return st
-
-    def _fill_noise(self, st, normals_sequence, total):
-        if self.ddim_eta and normals_sequence is not None:  # injected table (else: in-graph draws)
-            st["noise"].copy_(normals_sequence[:total])
 
     def _refresh(self):
         f = getattr(self.model, "refresh_hip_weights", None)
@@ -300,124 +270,63 @@ class DDIMSampler(object):
     def _loop_graph(self, cond, img, total, log_every_t, intermediates, normals_sequence, **extra):
         """The whole loop as one HIP graph (unrolled: step i's coefficients and timestep are
         kernel arguments / a static timestep row)."""
-        st = self._entry("loop", cond, img, total, log_every_t, normals_sequence is not None, **extra)
-        self._fill_noise(st, normals_sequence, total)
+        st = self._entry("loop", cond, img, total, log_every_t, normals_sequence, **extra)
         self._refresh()
         if st["graph"] is None:
             b = img.shape[0]
             steps = np.flip(self.ddim_timesteps)
             st["ts"] = torch.tensor(np.repeat(np.asarray(steps, dtype=np.int64)[:, None], b, axis=1), device=img.device)
             st["ts_col"] = st["ts"][:, 0].contiguous()  # one timestep per loop step (the FiLM table)
-            x0 = st["x"].clone()
-            self._loop_body(st, total)  # warm-up: allocations, kernel attributes, GEMM plans
-            st["x"].copy_(x0)
-            g = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
-                    self._loop_body(st, total)
-            torch.cuda.current_stream().wait_stream(s)
-            st["graph"] = g
-            st["x"].copy_(x0)
+            st["graph"] = capture(lambda: self._loop_body(st, total), restore=st["x"], warm=True)
         st["graph"].replay()
         for j in range(len(st["logs"])):
             intermediates["x_inter"].append(st["log_x"][j].clone())
             intermediates["pred_x0"].append(st["log_px0"][j].clone())
         return st["out"].clone(), intermediates
 
-    def _hip_executor(self):
-        """The bf16 HIP UNet executor behind the model (None: another backbone / precision)."""
-        um = getattr(getattr(self.model, "model", None), "diffusion_model", None)
-        if um is None or not hasattr(um, "executor") or getattr(um, "hip_precision", "bf16") == "fp32":
-            return None
-        return um.executor()
-
     def _loop_body(self, st, total):
         x, xn = st["x"], st["x2"]
         logs = st["logs"]
-        noise_n = st["noise"].shape[0]
-        # the conditioning is fixed and every row shares t within the loop: the executor computes the
-        # concept-token K / V once and the FiLM rows of all S steps in one pass at step 0
-        # (UNetExecutor.samp_ts / samp_i); ENCDIFF_DDIM_HOIST=0 recomputes them every step
-        ex = self._hip_executor() if HOIST else None
-        if ex is not None:
-            ex.samp_ts, ex.samp_i = st["ts_col"], None
-        um = self._borrow(True)
-        try:
-            self._loop_steps(st, total, x, xn, logs, noise_n, ex)
-        finally:
-            if ex is not None:
-                ex.samp_ts = ex.samp_i = None
-            if um is not None:
-                um.borrow_eps = False
-
-    def _borrow(self, on):
-        """Let the HIP UNet hand its eps buffer over without a copy: each loop step consumes e_t
-        (ddim_step) before the next forward overwrites it.  Returns the UNet (None: another backbone)."""
-        um = getattr(getattr(self.model, "model", None), "diffusion_model", None)
-        if um is None or not hasattr(um, "executor"):
-            return None
-        um.borrow_eps = on
-        return um
-
-    def _loop_steps(self, st, total, x, xn, logs, noise_n, ex):
-        for i in range(total):
-            index = total - i - 1
-            if ex is not None:
-                ex.samp_i = i
-            if st["mask"] is not None:
-                self._renoise(st, x, st["ts"][i], st["mnoise"][i if st["mnoise"].shape[0] > 1 else 0])
-            e_t = self.model.apply_model(x, st["ts"][i], st["cond"])
-            a_t, a_prev = float(self.ddim_alphas[index]), float(self.ddim_alphas_prev[index])
-            sigma, s1 = float(self.ddim_sigmas[index]), float(self.ddim_sqrt_one_minus_alphas[index])
-            if st["draw"]:
-                st["noise"][0].normal_()
-            z = st["noise"][i if noise_n > 1 else 0]
-            if st["codebook"] is not None:
-                ops.ddim_step_quantized(x, e_t.float().contiguous(), z, (a_t, a_prev, sigma, s1), st["codebook"], xn,
-                                        st["px0"])
-            else:
-                ops.ddim_step(x, e_t.float().contiguous(), z, a_t, a_prev, sigma, s1, xn, st["px0"])
-            x, xn = xn, x
-            if i in logs:
-                j = logs.index(i)
-                st["log_x"][j].copy_(x)
-                st["log_px0"][j].copy_(st["px0"])
+        # ENCDIFF_DDIM_HOIST=0 recomputes K / V and the FiLM rows every step
+        with unet_loop(self.model, st["ts_col"] if HOIST else None) as at:
+            for i in range(total):
+                index = total - i - 1
+                at(i)
+                if st["mask"] is not None:
+                    self._renoise(st, x, st["ts"][i], st["mz"].row(i))
+                e_t = self.model.apply_model(x, st["ts"][i], st["cond"])
+                a_t, a_prev = float(self.ddim_alphas[index]), float(self.ddim_alphas_prev[index])
+                sigma, s1 = float(self.ddim_sigmas[index]), float(self.ddim_sqrt_one_minus_alphas[index])
+                z = st["z"].row(i)
+                if st["codebook"] is not None:
+                    ops.ddim_step_quantized(x, e_t.float().contiguous(), z, (a_t, a_prev, sigma, s1), st["codebook"],
+                                            xn, st["px0"])
+                else:
+                    ops.ddim_step(x, e_t.float().contiguous(), z, a_t, a_prev, sigma, s1, xn, st["px0"])
+                x, xn = xn, x
+                if i in logs:
+                    j = logs.index(i)
+                    st["log_x"][j].copy_(x)
+                    st["log_px0"][j].copy_(st["px0"])
         st["out"] = x
 
     def _renoise(self, st, x, t_row, z):
         """Kernel (a) in front of the UNet: the known region of x re-noised to the step's t."""
-        if st["mdraw"]:
-            z.normal_()
         ops.masked_renoise(x, st["x0"], z, st["mask"], t_row, self.model.sqrt_alphas_cumprod,
                            self.model.sqrt_one_minus_alphas_cumprod)
 
     def _step_graph(self, cond, img, total, log_every_t, intermediates, normals_sequence, **extra):
         """Loops longer than GRAPH_MAX_STEPS: one captured step (coefficients, timestep and
         noise row looked up at a device step index), replayed S times."""
-        st = self._entry("step", cond, img, total, log_every_t, normals_sequence is not None, **extra)
-        self._fill_noise(st, normals_sequence, total)
+        st = self._entry("step", cond, img, total, log_every_t, normals_sequence, **extra)
         self._refresh()
         b = img.shape[0]
         if st["graph"] is None:
             dev = img.device
             st.update(t=torch.empty(b, device=dev, dtype=torch.long), idx=torch.zeros(1, device=dev, dtype=torch.int32),
-                      i=torch.zeros(1, device=dev, dtype=torch.long), zrow=torch.empty_like(img),
-                      mzrow=torch.empty_like(img))
-            x0 = st["x"].clone()
+                      i=torch.zeros(1, device=dev, dtype=torch.long))
             st["idx"].fill_(total - 1)
-            self._step_body(st)
-            st["x"].copy_(x0)
-            g = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
-                    self._step_body(st)
-            torch.cuda.current_stream().wait_stream(s)
-            st["graph"] = g
-            st["x"].copy_(x0)
+            st["graph"] = capture(lambda: self._step_body(st), restore=st["x"], warm=True)
         st["idx"].fill_(total - 1)
         st["i"].zero_()
         for i in range(total):
@@ -430,27 +339,12 @@ class DDIMSampler(object):
     def _step_body(self, st):
         idx = st["idx"]
         st["t"].copy_(self._ts.index_select(0, idx.long()).expand(st["t"].shape[0]))
-        if st["mask"] is not None:
-            if st["mnoise"].shape[0] > 1:  # re-noise row of loop step i (device counter)
-                st["mzrow"].copy_(st["mnoise"].index_select(0, st["i"]).view_as(st["mzrow"]))
-                mz = st["mzrow"]
-            else:
-                mz = st["mnoise"][0]
-            self._renoise(st, st["x"], st["t"], mz)
-        um = self._borrow(True)
-        try:
+        if st["mask"] is not None:  # the re-noise row is read (drawn) in front of the forward
+            self._renoise(st, st["x"], st["t"], st["mz"].row_at(st["i"]))
+        with unet_loop(self.model):
             e_t = self.model.apply_model(st["x"], st["t"], st["cond"])
-        finally:
-            if um is not None:
-                um.borrow_eps = False
-        if st["noise"].shape[0] > 1:  # noise row of loop step i (device counter)
-            st["zrow"].copy_(st["noise"].index_select(0, st["i"]).view_as(st["zrow"]))
-            z = st["zrow"]
-        else:
-            z = st["noise"][0]
-            if st["draw"]:
-                z.normal_()
-        if st["noise"].shape[0] > 1 or (st["mask"] is not None and st["mnoise"].shape[0] > 1):
+        z = st["z"].row_at(st["i"])
+        if st["z"].indexed or (st["mask"] is not None and st["mz"].indexed):
             st["i"].add_(1)  # the device counter of the injected tables
         if st["codebook"] is not None:
             ops.ddim_step_quantized(st["x"], e_t.float().contiguous(), z, self._coef, st["codebook"], st["x2"],
@@ -571,13 +465,9 @@ class DDIMSamplerAttn(DDIMSampler):
         x = latent.clone().detach()
         if self.use_graph and x.is_cuda and isinstance(cond, torch.Tensor):
             x = x.float().contiguous()
-            if total <= GRAPH_MAX_STEPS:
-                lk = ("inv", tuple(x.shape), total, self._sched_key, tuple(cond.shape), cond.dtype)
-                seen = self._seen.get(lk, 0)
-                self._seen[lk] = seen + 1
-                if seen >= LOOP_GRAPH_AFTER:
-                    return all_latent + self._inv_loop_graph(cond, x, total), intermediates
-            return all_latent + self._inv_step_graph(cond, x, total), intermediates
+            lk = ("inv", tuple(x.shape), total, self._sched_key, tuple(cond.shape), cond.dtype)
+            run = self._inv_loop_graph if self._path(lk, total) == "loop" else self._inv_step_graph
+            return all_latent + run(cond, x, total), intermediates
         b = x.shape[0]
         for i, step in enumerate(steps):
             ts = torch.full((b,), int(step), device=x.device, dtype=torch.long)
@@ -620,16 +510,6 @@ class DDIMSamplerAttn(DDIMSampler):
         st["traj"][0].copy_(x)
         return st
 
-    def _capture(self, body):
-        g = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
-                body()
-        torch.cuda.current_stream().wait_stream(s)
-        return g
-
     def _inv_loop_graph(self, cond, x, total):
         """The whole inversion loop as one HIP graph: step i reads slot i and writes slot i + 1 of
         the entry's trajectory buffer (no copy nodes); coefficients are kernel arguments."""
@@ -639,28 +519,18 @@ class DDIMSamplerAttn(DDIMSampler):
             ts = np.asarray(self.ddim_timesteps, dtype=np.int64)
             st["ts"] = torch.tensor(np.repeat(ts[:, None], x.shape[0], axis=1), device=x.device)
             st["ts_col"] = st["ts"][:, 0].contiguous()  # ascending: the FiLM table of the loop
-            self._inv_loop_body(st, total)  # warm-up (slot 0 is only read)
-            st["graph"] = self._capture(lambda: self._inv_loop_body(st, total))
+            # no restore: slot 0 is only read
+            st["graph"] = capture(lambda: self._inv_loop_body(st, total), warm=True)
         st["graph"].replay()
         return [st["traj"][k].clone() for k in range(1, total + 1)]
 
     def _inv_loop_body(self, st, total):
-        ex = self._hip_executor() if HOIST else None
-        if ex is not None:
-            ex.samp_ts, ex.samp_i = st["ts_col"], None
-        um = self._borrow(True)
         traj = st["traj"]
-        try:
+        with unet_loop(self.model, st["ts_col"] if HOIST else None) as at:
             for i in range(total):
-                if ex is not None:
-                    ex.samp_i = i
+                at(i)
                 e_t = self.model.apply_model(traj[i], st["ts"][i], st["cond"])
                 ops.ddim_invert_step(traj[i], e_t.float().contiguous(), self._inv_row(i), traj[i + 1])
-        finally:
-            if ex is not None:
-                ex.samp_ts = ex.samp_i = None
-            if um is not None:
-                um.borrow_eps = False
 
     def _inv_step_graph(self, cond, x, total):
         """One captured inversion step (timestep and coefficient row looked up at a device step
@@ -673,7 +543,7 @@ class DDIMSamplerAttn(DDIMSampler):
                       idx=torch.zeros(1, device=dev, dtype=torch.int32))
             self._inv_step_body(st)  # warm-up at row 0
             st["traj"][0].copy_(x)
-            st["graph"] = self._capture(lambda: self._inv_step_body(st))
+            st["graph"] = capture(lambda: self._inv_step_body(st))
         st["idx"].zero_()
         out = []
         for _ in range(total):
@@ -684,10 +554,6 @@ class DDIMSamplerAttn(DDIMSampler):
     def _inv_step_body(self, st):
         x, idx = st["traj"][0], st["idx"]
         st["t"].copy_(self._ts.index_select(0, idx.long()).expand(st["t"].shape[0]))
-        um = self._borrow(True)
-        try:
+        with unet_loop(self.model):
             e_t = self.model.apply_model(x, st["t"], st["cond"])
-        finally:
-            if um is not None:
-                um.borrow_eps = False
         ops.ddim_invert_step(x, e_t.float().contiguous(), self._inv_coef, x, index=idx, advance=True)

@@ -28,6 +28,7 @@ import torch
 from torch import nn
 
 from encdiff_amd import ops, torch_ops  # noqa: F401  (torch_ops registers torch.ops.encdiff.*)
+from encdiff_amd.graph_loops import NoiseRows, capture, kernel_mask, noise_table, unet_loop, vq_codebook
 from ...util import count_params, default, exists, instantiate_from_config
 from ...modules.diffusionmodules.util import extract_into_tensor, make_beta_schedule
 from ...modules.ema import LitEma
@@ -702,7 +703,7 @@ class LatentDiffusion(DDPM):
 
     def _ancestral_codebook(self, x):
         """The codebook for ops.ancestral_step's quantisation (the sampler's rule)."""
-        cb = self.ddim_sampler()._codebook(x)
+        cb = vq_codebook(self, x)
         if cb is None:
             raise NotImplementedError("quantize_denoised needs a VQ first stage whose codebook the HIP search "
                                       "covers (e_dim == latent channels <= 8, n_e <= 8192)")
@@ -721,17 +722,16 @@ class LatentDiffusion(DDPM):
             raise NotImplementedError("the HIP ancestral step covers the eps parameterisation")
         if not img.is_cuda:
             raise RuntimeError("the ancestral sampling loop runs on the HIP path")
-        from .ddim import DDIMSampler
         img = img.float().contiguous()
         b = img.shape[0]
         kmask = None
         if mask is not None:
             assert x0 is not None
-            kmask = DDIMSampler._kernel_mask(mask, img)
+            kmask = kernel_mask(mask, img)
             if kmask is None:
                 raise NotImplementedError(f"mask of shape {tuple(mask.shape)}: (B, 1, H, W) or (B, C, H, W) expected")
             x0 = x0.to(img.device).float().contiguous()
-        table = lambda seq, what: None if seq is None else DDIMSampler._noise_table(  # noqa: E731
+        table = lambda seq, what: None if seq is None else noise_table(  # noqa: E731
             seq, timesteps, img.shape, img.device, what)
         normals = table(normals_sequence, "normals_sequence")
         mnormals = table(mask_normals_sequence, "mask_normals_sequence")
@@ -775,8 +775,9 @@ class LatentDiffusion(DDPM):
 
     def _ancestral_graph(self, cond, img, timesteps, logs, log_x0, cb, kmask, x0, normals, mnormals):
         """One captured ancestral step (t, the coefficient row and the injected noise rows looked up
-        at device counters), replayed `timesteps` times.  Buffer discipline of
-        DDIMSampler._step_graph: x, the conditioning, mask and x0 are buffers of the cache entry."""
+        at device counters), replayed `timesteps` times.  Buffer discipline of DDIMSampler's one-step
+        graph: x, the conditioning, mask and x0 are buffers of the cache entry, the step noise and the
+        re-noise one graph_loops.NoiseRows each."""
         graphs = self.__dict__.setdefault("_anc_graphs", {})
         key = (tuple(img.shape), tuple(cond.shape), cond.dtype, cb is not None, bool(self.clip_denoised),
                None if kmask is None else (tuple(kmask.shape), mnormals is not None), normals is not None,
@@ -788,35 +789,22 @@ class LatentDiffusion(DDPM):
                 x=torch.empty_like(img), xr=torch.empty_like(img), cond=torch.empty_like(cond),
                 t=torch.empty(img.shape[0], device=dev, dtype=torch.long),
                 idx=torch.zeros(1, device=dev, dtype=torch.int32), i=torch.zeros(1, device=dev, dtype=torch.long),
-                noise=torch.zeros((timesteps if normals is not None else 1), *img.shape, device=dev),
-                zrow=torch.empty_like(img), graph=None, codebook=cb, mask=None, tab=self.ancestral_table())
+                z=NoiseRows(timesteps, img.shape, dev, normals is not None), graph=None, codebook=cb, mask=None,
+                tab=self.ancestral_table())
             if kmask is not None:
-                st.update(mask=torch.empty_like(kmask), x0=torch.empty_like(img), mzrow=torch.empty_like(img),
-                          mnoise=torch.zeros((timesteps if mnormals is not None else 1), *img.shape, device=dev))
+                st.update(mask=torch.empty_like(kmask), x0=torch.empty_like(img),
+                          mz=NoiseRows(timesteps, img.shape, dev, mnormals is not None))
         st["x"].copy_(img)
         st["cond"].copy_(cond)
-        if normals is not None:
-            st["noise"].copy_(normals[:timesteps])
+        st["z"].fill(normals)
         if kmask is not None:
             st["mask"].copy_(kmask)
             st["x0"].copy_(x0)
-            if mnormals is not None:
-                st["mnoise"].copy_(mnormals[:timesteps])
+            st["mz"].fill(mnormals)
         self.refresh_hip_weights()
         if st["graph"] is None:
-            keep = st["x"].clone()
             st["idx"].fill_(timesteps - 1)
-            self._ancestral_body(st)  # warm-up: allocations, kernel attributes, GEMM plans
-            st["x"].copy_(keep)
-            g = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
-                    self._ancestral_body(st)
-            torch.cuda.current_stream().wait_stream(s)
-            st["graph"] = g
-            st["x"].copy_(keep)
+            st["graph"] = capture(lambda: self._ancestral_body(st), restore=st["x"], warm=True)
         st["idx"].fill_(timesteps - 1)
         st["i"].zero_()
         out = []
@@ -829,28 +817,13 @@ class LatentDiffusion(DDPM):
     def _ancestral_body(self, st):
         x, idx = st["x"], st["idx"]
         st["t"].copy_(idx.long().expand(st["t"].shape[0]))  # t is the table row
-        um = self.model.diffusion_model
-        borrow = hasattr(um, "executor")  # the HIP UNet hands its eps buffer over: consumed before the next forward
-        if borrow:
-            um.borrow_eps = True
-        try:
+        with unet_loop(self):
             e = self.apply_model(x, st["t"], st["cond"])
-        finally:
-            if borrow:
-                um.borrow_eps = False
-
-        def row(table, buf):
-            if table.shape[0] > 1:  # injected: row of loop step i (device counter)
-                buf.copy_(table.index_select(0, st["i"]).view_as(buf))
-                return buf
-            table[0].normal_()
-            return table[0]
-
-        z = row(st["noise"], st["zrow"])
+        z = st["z"].row_at(st["i"])  # the step noise is read (drawn) after the forward, the re-noise after the step
         ops.ancestral_step(x, e.float().contiguous(), z, st["tab"], idx, x, st["xr"], clamp=self.clip_denoised,
                            advance=True, codebook=st["codebook"])
         if st["mask"] is not None:
-            ops.masked_renoise(x, st["x0"], row(st["mnoise"], st["mzrow"]), st["mask"], st["t"],
+            ops.masked_renoise(x, st["x0"], st["mz"].row_at(st["i"]), st["mask"], st["t"],
                                self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod)
         st["i"].add_(1)
 

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .graph_loops import capture
 from .ops import Geom
 from .unet import GN_FROM_PRODUCER
 
@@ -301,17 +302,6 @@ class VQDecoderExecutor(_VQExecutorBase):
         ops.small_conv_out_fwd(a, g, P["out.w"], P["out.b"], img)
         return img
 
-    def _capture(self, *key):
-        ops.flush()
-        gr = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(gr, stream=s, capture_error_mode="thread_local"):
-                self._run(*key)
-        torch.cuda.current_stream().wait_stream(s)
-        return gr
-
     @torch.no_grad()
     def decode(self, h: torch.Tensor, force_not_quantize=False, disentangled_repr=None) -> torch.Tensor:
         """h fp32 NCHW [B, e_dim, H, W] -> decoder(post_quant_conv(cat(quantize(h), repr))) fp32 NCHW."""
@@ -341,6 +331,7 @@ class VQDecoderExecutor(_VQExecutorBase):
         else:
             gr = self._graphs.get(key)
             if gr is None:
-                gr = self._graphs[key] = self._capture(*key)
+                ops.flush()
+                gr = self._graphs[key] = capture(lambda: self._run(*key))  # warmed up by the first, eager call
             gr.replay()
         return img.clone()
