@@ -91,12 +91,15 @@ def rnd(g, *shape, scale=1.0, dtype=F32, specials=False, tiny=True):
 class Guard:
     """A [rows][cols] view (row stride ld, first column at `left`) inside a flat sentinel-filled
     buffer with `pad` sentinels in front and behind; check() proves every element outside the view
-    is bitwise unchanged."""
+    is bitwise unchanged.  ld / left choose the row stride and first column themselves (odd strides,
+    misaligned views); fill: what the buffer holds around the view."""
 
-    def __init__(self, rows, cols, dtype, strided=False, init=None, pad=64):
-        ld, left = (cols + 24, 8) if strided else (cols, 0)
+    def __init__(self, rows, cols, dtype, strided=False, init=None, pad=64, ld=None, left=None, fill=SENT):
+        dld, dleft = (cols + 24, 8) if strided else (cols, 0)
+        ld, left = (dld if ld is None else ld), (dleft if left is None else left)
+        assert left + cols <= ld
         self.geom = ((rows, cols), (ld, 1), pad + left)
-        self.buf = torch.full((pad + rows * ld + pad,), SENT, dtype=dtype, device=dev)
+        self.buf = torch.full((pad + rows * ld + pad,), fill, dtype=dtype, device=dev)
         self.view = self.buf.as_strided(*self.geom)
         if init is not None:
             self.view.copy_(init)

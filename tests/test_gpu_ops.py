@@ -4,6 +4,8 @@ reference of the same op, evaluated on the same (bf16-rounded) inputs.
 Tolerances: bf16-output kernels rel-L2 <= 1e-2 (one bf16 rounding of the output,
 fp32 accumulation); fp32-output kernels (weight gradients) rel-L2 <= 2e-3.
 Attention is also tested per element, on every launch path, in test_gpu_attention.py.
+The GEMM / implicit-im2col engine (every tile, split-K form, halo / WG3 / WGL kernel, paired and
+grouped launch) is also tested per element, bitwise on exact integer cases, in test_gpu_gemm.py.
 """
 import math
 
