@@ -6,6 +6,8 @@ fp32 accumulation); fp32-output kernels (weight gradients) rel-L2 <= 2e-3.
 Attention is also tested per element, on every launch path, in test_gpu_attention.py.
 The GEMM / implicit-im2col engine (every tile, split-K form, halo / WG3 / WGL kernel, paired and
 grouped launch) is also tested per element, bitwise on exact integer cases, in test_gpu_gemm.py.
+The fused SpatialTransformer kernels (every row tile, wave count, statistics and key-gradient form)
+are also tested per element, stage by stage on their own saved tensors, in test_gpu_st.py.
 """
 import math
 
