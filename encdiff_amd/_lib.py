@@ -263,6 +263,11 @@ _PROTOS = {
     "encdiff_ddim_step_quantized": [C.POINTER(SamplerStepArgs), vp],
     "encdiff_ancestral_step": [C.POINTER(SamplerStepArgs), vp],
     "encdiff_ddim_invert_step": [C.POINTER(SamplerStepArgs), vp],
+    "encdiff_gather_colvar": [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp],
+    "encdiff_fvae_votes": [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_double, vp, vp, vp, vp],
+    "encdiff_mig_hist": [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(C.c_int), C.c_int, vp, vp, vp,
+                         vp],
+    "encdiff_mig_finalize": [vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, vp, vp, vp, vp],
     "encdiff_version": [],
 }
 

@@ -190,7 +190,7 @@ class DDPM(nn.Module):
         self.l_simple_weight = l_simple_weight
         if monitor is not None:
             self.monitor = monitor
-        self.eval_name = eval_name  # disentanglement metrics are out of scope
+        self.eval_name = eval_name  # names the factor grid of validation_metrics (encdiff_amd/metrics.py)
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys, only_model=load_only_unet)
         self.register_schedule(given_betas=given_betas, beta_schedule=beta_schedule, timesteps=timesteps,
@@ -905,8 +905,8 @@ class LatentDiffusion(DDPM):
     @torch.no_grad()
     def validation_step(self, batch, batch_idx=0):
         """ddpm_enc.py:377-390: concept tokens c (B, latent_unit, context_dim) and scalar codes
-        orc (B, latent_unit) of the batch, collected for the epoch-end metrics (eval_func is
-        out of scope; on_validation_epoch_end returns the stacked arrays)."""
+        orc (B, latent_unit) of the batch, collected for the epoch-end metrics
+        (on_validation_epoch_end returns the stacked arrays; validation_metrics scores the codes)."""
         x, oc = self.get_input(batch, self.first_stage_key)
         c, orc = self.encode_concepts(oc)
         if not hasattr(self, "validation_step_outputs"):
@@ -940,13 +940,15 @@ class LatentDiffusion(DDPM):
         return c.reshape(c.shape[0], self.model.diffusion_model.latent_unit, -1), orc
 
     @torch.no_grad()
-    def encode_dataset(self, pool, chunk=4096):
+    def encode_dataset(self, pool, chunk=2048):
         """Validation encoding pass over a GPU-resident uint8 image pool
         (encdiff_amd.data.ImagePool, or a uint8 [N, H, W, C] device tensor): fused
         gather + ToTensor/Normalize, the HIP Encoder4 trunk in eval mode, Linear and the warp
         MLPs, `chunk` images per pass, results kept on the device.  Returns (codes (N,
         latent_unit), tokens (N, latent_unit, context_dim)) in dataset order -- the arrays the
-        reference collects batch by batch through validation_step (ddpm_enc.py:377-390)."""
+        reference collects batch by batch through validation_step (ddpm_enc.py:377-390).
+        chunk * H * W must stay below 2^24 pixels, the im2col GEMM's index range: 4096 images of
+        64 x 64 are refused (ENCDIFF_ERR_SHAPE), hence 2048."""
         images = pool.images if hasattr(pool, "images") else pool
         n = images.shape[0]
         dev = images.device
@@ -964,6 +966,25 @@ class LatentDiffusion(DDPM):
             codes[s:s + b].copy_(orc)
             toks[s:s + b].copy_(c)
         return codes, toks
+
+    @torch.no_grad()
+    def validation_metrics(self, codes=None, pool=None, seed=0):
+        """The FactorVAE score and MIG of eval_func (main_val.py:74-94) on the device, under its
+        keys: {"factor_VAE": {train_accuracy, eval_accuracy, num_active_dims}, "MIG":
+        {discrete_mig}}.  codes: (N, latent_unit) scalar codes in dataset order (device tensor or
+        numpy), or pool: the validation image pool, encoded with encode_dataset.  The factor grid is
+        FactorGrid.named(self.eval_name).  beta-VAE and DCI (sklearn classifiers) are not computed."""
+        from encdiff_amd import metrics
+        if (codes is None) == (pool is None):
+            raise ValueError("validation_metrics takes either codes or pool")
+        grid = metrics.FactorGrid.named(self.eval_name)
+        if pool is not None:
+            n = (pool.images if hasattr(pool, "images") else pool).shape[0]
+            if n != grid.size:
+                raise ValueError(f"{n} images but the {self.eval_name} factor grid has {grid.size} observations")
+            codes = self.encode_dataset(pool)[0]
+        return {"factor_VAE": metrics.factor_vae_score(codes, grid, seed=seed),
+                "MIG": metrics.mig_score(codes, grid, seed=seed)}
 
     @torch.no_grad()
     def log_images(self, batch, N=8, n_row=4, sample=True, ddim_steps=200, ddim_eta=1., return_keys=None,

@@ -1,0 +1,210 @@
+"""Disentanglement metrics of the validation codes, scored on the device: the FactorVAE score
+(evaluation/metrics/factor_vae.py) and the mutual information gap (mig.py, utils.py) that the
+reference's eval_func (main_val.py:38-96) logs after every validation epoch.
+
+The reference scores a code table through a "representation function" that is a row lookup
+(``pca_rep[x]``) over "observations" that are dataset indices (``Dataset(np.arange(N))``).  Both
+metrics therefore reduce to index sampling (host, here), row gathers, variances, histograms and a few
+logarithms (csrc/metrics.hip).  The samplers below consume a ``numpy.random.RandomState`` in exactly
+the order the reference does, so a seed yields the reference's index tables; only the votes matrices
+(K x D integers), the D global variances and the MIG score come back to the host.
+
+Out of scope: beta-VAE and DCI (they train sklearn classifiers) and the per-token PCA eval_func
+applies to 3-D token arrays -- the scalar codes are scored, as the reference does when it has them.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+NUM_BINS = 20           # discretizer.num_bins of eval_func; fixed in the kernel
+MIG_BATCH = 16          # compute_mig's batch_size default: num_train is drawn 16 at a time
+MAX_FACTOR_VALUES = 256  # joint counts of one factor kept in LDS (csrc/metrics.hip)
+MAX_FACTORS = 16
+MAX_DIMS = 64
+
+# eval_name -> factor sizes: the grids ddpm_enc.py:122-130 of the reference binds eval_name to.
+# cars3d's index (data/ground_truth/cars3d.py) is a lookup built from sklearn's cartesian() of the
+# factor ranges, which enumerates them row-major: the lookup is the identity and the index is this
+# same mixed radix.
+_NAMED = {
+    "shapes3d": [10, 10, 10, 8, 4, 15],
+    "mpi3d": [6, 6, 2, 3, 3, 40, 40],
+    "cars3d": [4, 24, 183],
+}
+
+
+class FactorGrid:
+    """Full-grid ground truth in which every factor is latent: observation index
+    sum_k f_k * base_k with base_k = prod(sizes) / cumprod(sizes)[k] (row-major mixed radix)."""
+
+    def __init__(self, factor_sizes):
+        sizes = [int(v) for v in factor_sizes]
+        if not sizes or min(sizes) < 1:
+            raise ValueError(f"factor sizes must be positive, got {list(factor_sizes)}")
+        self.factor_sizes = sizes
+        self.num_factors = len(sizes)
+        self.size = int(np.prod(sizes, dtype=np.int64))
+        if self.size >= 2 ** 31:
+            raise ValueError(f"grid of {self.size} observations: index tables are int32")
+        self.bases = self.size // np.cumprod(sizes, dtype=np.int64)
+
+    @classmethod
+    def named(cls, eval_name):
+        if eval_name not in _NAMED:
+            raise ValueError(f"eval_name {eval_name!r} has no ground-truth factor grid "
+                             f"(known: {sorted(_NAMED)}); the disentanglement metrics need one")
+        return cls(_NAMED[eval_name])
+
+    def sample_factors(self, num, random_state):
+        """(num, K) int64: one randint(size_k, size=num) per factor, in factor order."""
+        out = np.empty((num, self.num_factors), dtype=np.int64)
+        for k, size in enumerate(self.factor_sizes):
+            out[:, k] = random_state.randint(size, size=num)
+        return out
+
+    def index(self, factors):
+        return np.asarray(factors, dtype=np.int64) @ self.bases
+
+    def __repr__(self):
+        return f"FactorGrid({self.factor_sizes})"
+
+
+# ------------------------------------------------------------------ index samplers (host)
+def sample_variance_indices(grid, random_state, num_variance_estimate):
+    """var_idx int32 (V,): the rows of the global variance estimate (one sample_factors call)."""
+    return grid.index(grid.sample_factors(num_variance_estimate, random_state)).astype(np.int32)
+
+
+def sample_votes(grid, random_state, batch_size, num_points):
+    """vote_idx int32 (P, batch) and vote_factor int32 (P,): per vote randint(num_factors), then
+    sample_factors(batch_size), then the chosen column set to its row-0 value."""
+    idx = np.empty((num_points, batch_size), dtype=np.int32)
+    fac = np.empty(num_points, dtype=np.int32)
+    for p in range(num_points):
+        k = random_state.randint(grid.num_factors)
+        f = grid.sample_factors(batch_size, random_state)
+        f[:, k] = f[0, k]
+        idx[p] = grid.index(f)
+        fac[p] = k
+    return idx, fac
+
+
+def sample_mig(grid, random_state, num_train):
+    """mig_idx int32 (M,) and mig_factors int32 (K, M): ceil(num_train / 16) draws of 16 (the last
+    one shorter), as utils.generate_batch_factor_code does."""
+    parts = []
+    i = 0
+    while i < num_train:
+        n = min(num_train - i, MIG_BATCH)
+        parts.append(grid.sample_factors(n, random_state))
+        i += n
+    f = np.concatenate(parts, 0)
+    return grid.index(f).astype(np.int32), np.ascontiguousarray(f.T).astype(np.int32)
+
+
+def accuracy_from_votes(train_votes, eval_votes):
+    """(train_accuracy, eval_accuracy): classifier = argmax(train_votes, axis=0); each accuracy is
+    the votes under the classifier over all votes (factor_vae.py:77-93)."""
+    train_votes, eval_votes = np.asarray(train_votes, np.int64), np.asarray(eval_votes, np.int64)
+    classifier = np.argmax(train_votes, axis=0)
+    other = np.arange(train_votes.shape[1])
+    train = np.sum(train_votes[classifier, other]) * 1. / np.sum(train_votes)
+    ev = np.sum(eval_votes[classifier, other]) * 1. / np.sum(eval_votes)
+    return float(train), float(ev)
+
+
+# ------------------------------------------------------------------ checks (host, before any launch)
+def _check_codes(codes, grid):
+    if codes.ndim != 2:
+        raise ValueError(f"codes must be (N, D) scalar codes, got shape {tuple(codes.shape)}; the PCA of "
+                         f"(N, units, dim) tokens is out of scope")
+    n, d = codes.shape
+    if n != grid.size:
+        raise ValueError(f"{n} code rows but the factor grid {grid.factor_sizes} has {grid.size} observations")
+    if not 1 <= d <= MAX_DIMS:
+        raise ValueError(f"{d} code dimensions: the metric kernels take 1..{MAX_DIMS}")
+
+
+def _check_mig(grid, num_bins, dims):
+    if num_bins != NUM_BINS:
+        raise ValueError(f"num_bins={num_bins}: the histogram kernel is built for {NUM_BINS} bins")
+    big = [v for v in grid.factor_sizes if v > MAX_FACTOR_VALUES]
+    if big:
+        raise ValueError(f"factor sizes {big}: MIG counts at most {MAX_FACTOR_VALUES} values of a factor "
+                         f"(V_k <= {MAX_FACTOR_VALUES})")
+    if grid.num_factors > MAX_FACTORS:
+        raise ValueError(f"{grid.num_factors} factors: MIG takes at most {MAX_FACTORS}")
+    if dims < 2:
+        raise ValueError("MIG needs at least two code dimensions (the gap between the two largest MI)")
+
+
+def _device_codes(codes):
+    import torch
+    if isinstance(codes, np.ndarray):
+        codes = torch.from_numpy(np.ascontiguousarray(codes, dtype=np.float32))
+    if not codes.is_cuda:
+        if not torch.cuda.is_available():
+            raise RuntimeError("the disentanglement metrics run on the HIP device; there is no CPU fallback")
+        codes = codes.cuda()
+    return codes.detach().to(torch.float32).contiguous()
+
+
+def _up(a, device):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+
+# ------------------------------------------------------------------ scores
+def factor_vae_score(codes, grid, seed=0, batch_size=64, num_train=10000, num_eval=5000,
+                     num_variance_estimate=10000, prune_threshold=0.05):
+    """compute_factor_vae of the reference with eval_func's bindings as defaults.  codes: (N, D)
+    device tensor (or numpy, uploaded), N == grid.size.  Returns {"train_accuracy", "eval_accuracy",
+    "num_active_dims"}; num_active_dims is the length of the mask, i.e. D, as the reference returns
+    it, and 0 with both accuracies 0 when no dimension is active."""
+    _check_codes(codes, grid)
+    if not 2 <= batch_size <= 64:
+        raise ValueError(f"batch_size={batch_size}: the vote kernel takes 2..64 rows per point")
+    import torch
+    from . import ops
+    rs = np.random.RandomState(seed)
+    var_idx = sample_variance_indices(grid, rs, num_variance_estimate)
+    codes = _device_codes(codes)
+    dev, (_, D), K = codes.device, codes.shape, grid.num_factors
+    gvar = torch.empty(D, device=dev, dtype=torch.float64)
+    ops.gather_colvar(codes, _up(var_idx, dev), gvar)
+    active = np.sqrt(gvar.cpu().numpy()) >= prune_threshold
+    if not active.any():
+        return {"train_accuracy": 0., "eval_accuracy": 0., "num_active_dims": 0}
+    votes = []
+    for num in (num_train, num_eval):
+        idx, fac = sample_votes(grid, rs, batch_size, num)
+        v = torch.empty(K, D, device=dev, dtype=torch.int32)
+        ops.fvae_votes(codes, _up(idx, dev), _up(fac, dev), K, gvar, prune_threshold, v)
+        votes.append(v)
+    train, ev = accuracy_from_votes(votes[0].cpu().numpy(), votes[1].cpu().numpy())
+    return {"train_accuracy": train, "eval_accuracy": ev, "num_active_dims": int(len(active))}
+
+
+def mig_score(codes, grid, seed=0, num_train=10000, num_bins=NUM_BINS, edge_f64=None):
+    """compute_mig of the reference with eval_func's bindings (histogram discretiser, 20 bins).
+    Returns {"discrete_mig"}.  edge_f64: evaluate the histogram edges as NumPy 1.x does (float64,
+    rounded to float32 at the end) or as NumPy >= 2 does (float32 throughout); the two differ by at
+    most an ulp of an edge.  None: as the installed NumPy does, i.e. what the reference's
+    np.histogram would give in this environment."""
+    _check_codes(codes, grid)
+    _check_mig(grid, num_bins, codes.shape[1])
+    if edge_f64 is None:
+        edge_f64 = int(np.__version__.split(".")[0]) < 2
+    import torch
+    from . import ops
+    idx, fac = sample_mig(grid, np.random.RandomState(seed), num_train)
+    codes = _device_codes(codes)
+    dev, (_, D), K = codes.device, codes.shape, grid.num_factors
+    edges = torch.empty(D, NUM_BINS, device=dev, dtype=torch.float32)
+    counts = torch.empty(ops.mig_counts_shape(D, grid.factor_sizes), device=dev, dtype=torch.int32)
+    mi = torch.empty(D, K, device=dev, dtype=torch.float64)
+    h = torch.empty(K, device=dev, dtype=torch.float64)
+    score = torch.empty(1, device=dev, dtype=torch.float64)
+    ops.mig_hist(codes, _up(idx, dev), _up(fac, dev), grid.factor_sizes, edges, counts, edge_f64=edge_f64)
+    ops.mig_finalize(counts, grid.factor_sizes, idx.shape[0], mi, h, score)
+    return {"discrete_mig": float(score.item())}

@@ -1520,6 +1520,88 @@ def encoder_warp_bwd(u, params, unit_stride, units, context_dim, dout, du, grads
           "encdiff_encoder_warp_bwd")
 
 
+# ------------------------------------------------------------------ disentanglement metrics
+METRICS_MAX_DIMS, METRICS_BINS, METRICS_MAX_VALUES, METRICS_MAX_FACTORS = 64, 20, 256, 16
+
+
+def _dev(t, dtype, shape, what):
+    assert t.is_cuda, f"{what}: HIP device tensor required"
+    assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape), \
+        f"{what}: contiguous {dtype} {tuple(shape)} expected, got {t.dtype} {tuple(t.shape)}"
+    return t
+
+
+def _codes(codes):
+    assert codes.dim() == 2 and 1 <= codes.shape[1] <= METRICS_MAX_DIMS, \
+        f"codes: (N, D) with D <= {METRICS_MAX_DIMS} expected, got {tuple(codes.shape)}"
+    return _dev(codes, F32, codes.shape, "codes")
+
+
+def _factor_sizes(sizes):
+    sizes = [int(v) for v in sizes]
+    if not 1 <= len(sizes) <= METRICS_MAX_FACTORS:
+        raise ValueError(f"{len(sizes)} factors: the MIG kernels take 1..{METRICS_MAX_FACTORS}")
+    big = [v for v in sizes if not 1 <= v <= METRICS_MAX_VALUES]
+    if big:
+        raise ValueError(f"factor sizes {big}: the MIG kernels count at most {METRICS_MAX_VALUES} values of a "
+                         f"factor (V_k <= {METRICS_MAX_VALUES})")
+    return (C.c_int * len(sizes))(*sizes), max(sizes)
+
+
+def gather_colvar(codes, idx, out):
+    """out fp64 [D] = np.var(codes[idx], axis=0, ddof=1), two-pass in fp64 (encdiff_gather_colvar)."""
+    N, D = _codes(codes).shape
+    _dev(idx, torch.int32, (idx.numel(),), "idx"), _dev(out, torch.float64, (D,), "out")
+    check(lib.encdiff_gather_colvar(_p(codes), N, D, _p(idx), idx.numel(), _p(out), _s()), "encdiff_gather_colvar")
+
+
+def fvae_votes(codes, vote_idx, vote_factor, num_factors, global_var, threshold, votes, argmin=None, ratio=None):
+    """FactorVAE votes of the points vote_idx int32 [P][batch] / vote_factor int32 [P] into votes
+    int32 [K][D] (zeroed here); optional argmin int32 [P] and ratio fp64 [P][D] (encdiff_fvae_votes)."""
+    N, D = _codes(codes).shape
+    assert vote_idx.dim() == 2
+    P, batch = vote_idx.shape
+    _dev(vote_idx, torch.int32, (P, batch), "vote_idx"), _dev(vote_factor, torch.int32, (P,), "vote_factor")
+    _dev(global_var, torch.float64, (D,), "global_var"), _dev(votes, torch.int32, (num_factors, D), "votes")
+    if argmin is not None:
+        _dev(argmin, torch.int32, (P,), "argmin")
+    if ratio is not None:
+        _dev(ratio, torch.float64, (P, D), "ratio")
+    check(lib.encdiff_fvae_votes(_p(codes), N, D, _p(vote_idx), _p(vote_factor), P, batch, num_factors,
+                                 _p(global_var), float(threshold), _p(votes), _p(argmin), _p(ratio), _s()),
+          "encdiff_fvae_votes")
+
+
+def mig_counts_shape(dims, factor_sizes):
+    return (dims, len(factor_sizes), METRICS_BINS, max(int(v) for v in factor_sizes))
+
+
+def mig_hist(codes, mig_idx, mig_factors, factor_sizes, edges, counts, bins=None, edge_f64=False):
+    """Histogram discretiser and joint counts of MIG over codes[mig_idx]: edges fp32 [D][20], counts
+    int32 mig_counts_shape(D, factor_sizes) (zeroed here), optional bins int32 [D][M]
+    (encdiff_mig_hist).  mig_factors int32 [K][M]."""
+    N, D = _codes(codes).shape
+    sz, vmax = _factor_sizes(factor_sizes)
+    K, M = len(factor_sizes), mig_idx.numel()
+    _dev(mig_idx, torch.int32, (M,), "mig_idx"), _dev(mig_factors, torch.int32, (K, M), "mig_factors")
+    _dev(edges, F32, (D, METRICS_BINS), "edges"), _dev(counts, torch.int32, (D, K, METRICS_BINS, vmax), "counts")
+    if bins is not None:
+        _dev(bins, torch.int32, (D, M), "bins")
+    check(lib.encdiff_mig_hist(_p(codes), N, D, _p(mig_idx), M, _p(mig_factors), K, sz, int(bool(edge_f64)),
+                               _p(edges), _p(bins), _p(counts), _s()), "encdiff_mig_hist")
+
+
+def mig_finalize(counts, factor_sizes, m, mi, h, score):
+    """mi fp64 [D][K], h fp64 [K] and score fp64 [1] (discrete_mig) from mig_hist's counts over m rows
+    (encdiff_mig_finalize)."""
+    sz, vmax = _factor_sizes(factor_sizes)
+    D, K = counts.shape[0], len(factor_sizes)
+    _dev(counts, torch.int32, (D, K, METRICS_BINS, vmax), "counts")
+    _dev(mi, torch.float64, (D, K), "mi"), _dev(h, torch.float64, (K,), "h"), _dev(score, torch.float64, (1,), "score")
+    check(lib.encdiff_mig_finalize(_p(counts), D, K, sz, int(m), _p(mi), _p(h), _p(score), _s()),
+          "encdiff_mig_finalize")
+
+
 # ------------------------------------------------------------------ fp32 (ENCDIFF_DT_F32) forward
 # The reference-precision forms of the same entry points (include/encdiff_hip.h "dtype"): fp32
 # activations end to end, for the fp32 parity path (unet_f32.py).

@@ -973,6 +973,65 @@ int encdiff_ancestral_step(const EncdiffSamplerStepArgs* args, void* stream);
  *   batch, c or hw <= 0, or batch * c * hw >= 2^31: ENCDIFF_ERR_SHAPE. */
 int encdiff_ddim_invert_step(const EncdiffSamplerStepArgs* args, void* stream);
 
+/* ---------------------------------------------------------------- disentanglement metrics
+ * The array work of the FactorVAE score (evaluation/metrics/factor_vae.py) and of the mutual
+ * information gap (mig.py; utils.py _histogram_discretize, discrete_mutual_info) over a device code
+ * table codes fp32 [n_rows][dims], dims <= 64.  The reference's representation function is a row
+ * lookup, so each entry point gathers rows through an int32 index table sampled on the host
+ * (encdiff_amd/metrics.py).  All tables and outputs are device memory unless marked (host).
+ * Sums are fp64 in a fixed order with no floating-point atomics: a second launch gives the same
+ * bits.  Nothing is read back or allocated, so every entry point can be graph-captured.
+ * Row indices are clamped to [0, n_rows); factor values outside [0, V_k) are not counted.
+ * Refusals: a required pointer NULL: ENCDIFF_ERR_ARG; a size outside the stated limits:
+ * ENCDIFF_ERR_SHAPE.  Nothing is launched then. */
+#define ENCDIFF_METRICS_MAX_DIMS 64
+#define ENCDIFF_METRICS_BINS 20
+#define ENCDIFF_METRICS_MAX_VALUES 256
+#define ENCDIFF_METRICS_MAX_FACTORS 16
+
+/* var_out fp64 [dims]: the unbiased (ddof = 1) variance of every column over the rows
+ * codes[idx[i]], i < n (np.var(..., axis=0, ddof=1) of factor_vae.py _compute_variances).  Two
+ * passes, mean first.  n >= 2. */
+int encdiff_gather_colvar(const float* codes, int n_rows, int dims, const int* idx, int n, double* var_out,
+                          void* stream);
+
+/* FactorVAE votes (factor_vae.py _generate_training_batch).  For each point p < points: the ddof = 1
+ * variance (two-pass) of every column over the rows codes[vote_idx[p][r]], r < batch, divided by
+ * global_var[d]; the argmin over the ACTIVE dimensions, those with sqrt(global_var[d]) >= threshold,
+ * lowest index on a tie.  As in the reference the argmin is the position in the compacted list of
+ * active dimensions, not the dimension itself, and the vote is filed as
+ * votes[vote_factor[p]][argmin] += 1: a pruned dimension shifts the later columns left.
+ * votes int32 [num_factors][dims] is zeroed by the call.  Optional outputs (NULL: not written):
+ * argmin_out int32 [points] (-1 when no dimension is active; no vote is cast then) and ratio_out
+ * fp64 [points][dims], +inf at pruned dimensions.  2 <= batch <= 64. */
+int encdiff_fvae_votes(const float* codes, int n_rows, int dims, const int* vote_idx, const int* vote_factor,
+                       int points, int batch, int num_factors, const double* global_var, double threshold,
+                       int* votes, int* argmin_out, double* ratio_out, void* stream);
+
+/* MIG, first half, over the gathered rows codes[mig_idx[i]], i < m, per dimension d:
+ *   edges fp32 [dims][20]: np.histogram(column, 20)[1][:-1] for float32 data, i.e. the first 20 of
+ *     np.linspace(min, max, 21, dtype=float32) (min - 0.5, max + 0.5 when min == max): step =
+ *     (last - first) / 20, edge_i = i * step + first, product and sum rounded separately.
+ *     edge_f64 == 0: evaluated in float32, as NumPy >= 2 does; edge_f64 != 0: evaluated in float64
+ *     and each edge rounded to float32, as NumPy 1.x does.
+ *   bins_out int32 [dims][m] (optional): np.digitize(column, edges) = #{i : edge_i <= x}, in 1..20.
+ *   counts int32 [dims][num_factors][20][vmax], vmax = max_k factor_sizes[k], zeroed by the call:
+ *     counts[d][k][bin - 1][v] = #{i : bin_d(i) == bin and mig_factors[k][i] == v}.
+ * mig_factors int32 [num_factors][m]; factor_sizes (host) int [num_factors], each in 1..256;
+ * num_factors <= 16. */
+int encdiff_mig_hist(const float* codes, int n_rows, int dims, const int* mig_idx, int m, const int* mig_factors,
+                     int num_factors, const int* factor_sizes, int edge_f64, float* edges, int* bins_out,
+                     int* counts, void* stream);
+
+/* MIG, second half, from encdiff_mig_hist's counts (same factor_sizes (host), m), fp64, natural log:
+ *   mi [dims][num_factors] = sum over the non-zero cells of n/m * log(m n / (a_bin b_v)), a and b
+ *     the marginals of the cell's row and column (sklearn.metrics.mutual_info_score; clipped at 0);
+ *   h [num_factors] = MI(y_k, y_k), the entropy of factor k;
+ *   score [1] = mean_k (top1 - top2) / h[k], top1 >= top2 the two largest mi[:, k] (mig.py
+ *     _compute_mig's discrete_mig).  dims >= 2. */
+int encdiff_mig_finalize(const int* counts, int dims, int num_factors, const int* factor_sizes, int m, double* mi,
+                         double* h, double* score, void* stream);
+
 /* Library/device information (for tests): returns the number of exported kernels. */
 int encdiff_version(void);
 
