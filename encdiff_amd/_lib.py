@@ -268,6 +268,10 @@ _PROTOS = {
     "encdiff_mig_hist": [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(C.c_int), C.c_int, vp, vp, vp,
                          vp],
     "encdiff_mig_finalize": [vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, vp, vp, vp, vp],
+    "encdiff_tad_range": [vp, C.c_longlong, C.c_int, vp, vp, vp, vp, vp],
+    "encdiff_tad_counts": [vp, vp, C.c_longlong, C.c_int, C.c_int, vp, vp, vp],
+    "encdiff_tad_label_joint": [vp, C.c_longlong, C.c_int, vp, vp],
+    "encdiff_tad_auroc": [vp, vp, vp, vp, C.c_longlong, C.c_int, C.c_int, vp, vp],
     "encdiff_version": [],
 }
 

@@ -987,6 +987,25 @@ class LatentDiffusion(DDPM):
                 "MIG": metrics.mig_score(codes, grid, seed=seed)}
 
     @torch.no_grad()
+    def attribute_metrics(self, attributes, tokens=None, pool=None, thresh=0.75, ent_red_thresh=0.2):
+        """TAD of celeba_tad.py on the device, for models whose data carries binary attributes and no
+        factor grid (eval_name "celeba"): {"TAD": {tad_score, attributes_captured}, "per_attribute":
+        {max_auroc, argmax_latent, auroc_diff, norm_diff, ent_red_prop, captured}}, indexed by
+        attribute.  attributes: (N, A) labels in {0, 1}, A <= 64.  tokens: the concept tokens
+        (N, latent_unit, context_dim), or already flattened unit-major (N, L); or pool: the image
+        pool, encoded with encode_dataset."""
+        from encdiff_amd import metrics
+        if (tokens is None) == (pool is None):
+            raise ValueError("attribute_metrics takes either tokens or pool")
+        if pool is not None:
+            tokens = self.encode_dataset(pool)[1]
+        if tokens.ndim == 3:
+            tokens = tokens.reshape(tokens.shape[0], -1)
+        res = metrics.tad_score(tokens, attributes, thresh=thresh, ent_red_thresh=ent_red_thresh)
+        head = {k: res.pop(k) for k in ("tad_score", "attributes_captured")}
+        return {"TAD": head, "per_attribute": res}
+
+    @torch.no_grad()
     def log_images(self, batch, N=8, n_row=4, sample=True, ddim_steps=200, ddim_eta=1., return_keys=None,
                    quantize_denoised=True, inpaint=True, plot_denoise_rows=False, plot_progressive_rows=True,
                    sample_swap=False, plot_diffusion_rows=True, **kwargs):

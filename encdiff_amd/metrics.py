@@ -9,6 +9,10 @@ logarithms (csrc/metrics.hip).  The samplers below consume a ``numpy.random.Rand
 the order the reference does, so a seed yields the reference's index tables; only the votes matrices
 (K x D integers), the D global variances and the MIG score come back to the host.
 
+CelebA has no factor grid; its models are scored with TAD (celeba_tad.py; ae_utils_exp.py
+aurocs_search) from the 40 binary attributes: per (attribute, token column) ROC areas from integer
+counts (csrc/tad.hip), then a few hundred numbers of host arithmetic -- the last section below.
+
 Out of scope: beta-VAE and DCI (they train sklearn classifiers) and the per-token PCA eval_func
 applies to 3-D token arrays -- the scalar codes are scored, as the reference does when it has them.
 """
@@ -208,3 +212,124 @@ def mig_score(codes, grid, seed=0, num_train=10000, num_bins=NUM_BINS, edge_f64=
     ops.mig_hist(codes, _up(idx, dev), _up(fac, dev), grid.factor_sizes, edges, counts, edge_f64=edge_f64)
     ops.mig_finalize(counts, grid.factor_sizes, idx.shape[0], mi, h, score)
     return {"discrete_mig": float(score.item())}
+
+
+# ------------------------------------------------------------------ TAD (CelebA attributes)
+TAD_MAX_ATTRS = 64      # one packed label word per row (csrc/tad.hip)
+
+
+def pack_attributes(targ):
+    """(N, A) labels in {0, 1} (bool, int or float; device tensor or numpy) -> one word per row, bit a
+    = attribute a, a uint64 stored as int64 (numpy in, numpy out; tensor in, tensor on its device
+    out).  ValueError on a value outside {0, 1} or A > 64."""
+    shape = tuple(targ.shape)
+    if len(shape) != 2 or shape[1] < 1:
+        raise ValueError(f"attributes must be (N, A) labels, got shape {shape}")
+    if shape[1] > TAD_MAX_ATTRS:
+        raise ValueError(f"{shape[1]} attributes: a row's labels are packed into one 64-bit word "
+                         f"(A <= {TAD_MAX_ATTRS})")
+    if isinstance(targ, np.ndarray):
+        if not np.isin(targ, (0, 1)).all():
+            raise ValueError("attribute labels must be 0 or 1")
+        bits = targ.astype(np.uint64) << np.arange(shape[1], dtype=np.uint64)
+        return np.bitwise_or.reduce(bits, axis=1).view(np.int64)
+    import torch
+    if bool(((targ != 0) & (targ != 1)).any()):
+        raise ValueError("attribute labels must be 0 or 1")
+    # int64 shifts and sums wrap: bit 63 is the sign bit of the stored word
+    return ((targ != 0).to(torch.int64) << torch.arange(shape[1], device=targ.device)).sum(1)
+
+
+def tad_thresholds():
+    """The 11 classifier thresholds of calculate_auroc, from torch as the reference takes them."""
+    import torch
+    return torch.arange(0.0, 1.0001, step=0.1)
+
+
+def tad_aurocs(z, targ):
+    """aurocs_search of the reference on the device.  z: (N, L) float32, the flattened concept
+    tokens; targ: (N, A) labels in {0, 1}.  Returns device tensors {"aurocs" (A, L) float32,
+    "base_rates" (A,) float32, "label_joint" (A, A) int32, "col_max" (L,), "col_min" (L,)}.
+    ValueError when an attribute is constant (base rate 0 or 1: its ROC divides 0 by 0)."""
+    if z.ndim != 2:
+        raise ValueError(f"z must be the (N, L) table of flattened tokens, got shape {tuple(z.shape)}")
+    if targ.ndim != 2 or targ.shape[0] != z.shape[0]:
+        raise ValueError(f"{z.shape[0]} rows of z but attributes of shape {tuple(targ.shape)}")
+    if z.shape[0] < 1 or z.shape[1] < 1:
+        raise ValueError(f"z of shape {tuple(z.shape)} is empty")
+    packed = pack_attributes(targ)
+    import torch
+    from . import ops
+    z = _device_codes(z)
+    dev, (N, Lc), A = z.device, z.shape, targ.shape[1]
+    packed = _up(packed, dev) if isinstance(packed, np.ndarray) else packed.to(dev).contiguous()
+    f32 = dict(device=dev, dtype=torch.float32)
+    col_max, col_min, thr = torch.empty(Lc, **f32), torch.empty(Lc, **f32), torch.empty(Lc, ops.TAD_THRESHOLDS, **f32)
+    counts = torch.empty(ops.tad_counts_shape(Lc, A), device=dev, dtype=torch.int32)
+    joint = torch.empty(A, A, device=dev, dtype=torch.int32)
+    aurocs = torch.empty(A, Lc, **f32)
+    ops.tad_range(z, tad_thresholds().to(dev), col_max, col_min, thr)
+    ops.tad_counts(z, packed, A, thr, counts)
+    ops.tad_label_joint(packed, A, joint)
+    ops.tad_auroc(counts, joint, col_max, col_min, N, aurocs)
+    pos = joint.diagonal().cpu().numpy()
+    const = np.nonzero((pos == 0) | (pos == N))[0]
+    if const.size:
+        raise ValueError(f"attribute {int(const[0])} is constant over the {N} rows (base rate "
+                         f"{int(pos[const[0]] == N)}): its ROC is undefined")
+    # tensor / tensor: one correctly rounded float32 division, as targ.sum(0) / N of the reference
+    base = joint.diagonal().to(torch.float32) / torch.full((A,), float(N), **f32)
+    return {"aurocs": aurocs, "base_rates": base, "label_joint": joint, "col_max": col_max, "col_min": col_min}
+
+
+def label_mutual_information(label_joint, n):
+    """(A, A) float64: the mutual information (natural log) of every pair of binary labels from their
+    joint counts, celeba_tad.py:72-104: the sum over the cells FF, FT, TF, TT of jp * log(jp /
+    (pi * pj)), a cell with a zero probability contributing 0."""
+    tt = np.asarray(label_joint, np.float64)
+    p = np.diag(tt)
+    pi, pj = p[:, None], p[None, :]
+    cells = ((n - pi - pj + tt, n - pi, n - pj), (pj - tt, n - pi, pj), (pi - tt, pi, n - pj), (tt, pi, pj))
+    mi = np.zeros_like(tt)
+    for joint, mi_count, mj_count in cells:
+        jp, qi, qj = joint / n, np.broadcast_to(mi_count / n, tt.shape), np.broadcast_to(mj_count / n, tt.shape)
+        ok = (jp != 0) & (qi != 0) & (qj != 0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mi += np.where(ok, jp * np.log(jp / (qi * qj)), 0.0)
+    return mi
+
+
+def tad_from_aurocs(aurocs, label_joint, n, thresh=0.75, ent_red_thresh=0.2):
+    """The script half of celeba_tad.py (47-120) in float64 on the host, from aurocs (A, L) and the
+    label joint counts over n rows.  Per attribute: max_auroc and argmax_latent over the columns;
+    auroc_diff = max_auroc minus the largest other column (the argmax column set to 0); norm_diff =
+    1 - the largest other (auroc - 0.5) / (max_auroc - 0.5); ent_red_prop = 1 - (MI[i][i] - max_{j
+    != i} MI[i][j]) / MI[i][i].  captured = (max_auroc >= thresh) & (ent_red_prop <= ent_red_thresh);
+    tad_score = the sum of auroc_diff over the captured attributes."""
+    au = np.array(aurocs, dtype=np.float64)
+    A = au.shape[0]
+    rows = np.arange(A)
+    argmax = np.argmax(au, axis=1)
+    max_aur = au[rows, argmax]
+    nxt = au.copy()
+    nxt[rows, argmax] = 0.0
+    diff = max_aur - nxt.max(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        norm = (au - 0.5) / (max_aur - 0.5)[:, None]
+    norm[rows, argmax] = 0.0
+    norm_diff = 1.0 - norm.max(axis=1)
+    mi = label_mutual_information(label_joint, n)
+    others = (mi * (1.0 - np.eye(A))).max(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ent_red_prop = 1.0 - (np.diag(mi) - others) / np.diag(mi)
+    captured = (max_aur >= thresh) & (ent_red_prop <= ent_red_thresh)
+    return {"tad_score": float(diff[captured].sum()), "attributes_captured": int(captured.sum()),
+            "max_auroc": max_aur, "argmax_latent": argmax, "auroc_diff": diff, "norm_diff": norm_diff,
+            "ent_red_prop": ent_red_prop, "captured": captured}
+
+
+def tad_score(z, targ, thresh=0.75, ent_red_thresh=0.2):
+    """tad_aurocs, then tad_from_aurocs on its (A, L) areas and joint counts read back."""
+    res = tad_aurocs(z, targ)
+    return tad_from_aurocs(res["aurocs"].cpu().numpy(), res["label_joint"].cpu().numpy(), int(z.shape[0]),
+                           thresh=thresh, ent_red_thresh=ent_red_thresh)

@@ -1602,6 +1602,68 @@ def mig_finalize(counts, factor_sizes, m, mi, h, score):
           "encdiff_mig_finalize")
 
 
+# ------------------------------------------------------------------ TAD (CelebA attribute metric)
+TAD_THRESHOLDS, TAD_MAX_ATTRS, TAD_COL_TILE, TAD_ROW_STEP = 11, 64, 32, 512
+
+
+def _tad_z(z):
+    assert z.dim() == 2 and z.shape[0] >= 1 and z.shape[1] >= 1, f"z: (N, L) expected, got {tuple(z.shape)}"
+    return _dev(z, F32, z.shape, "z")
+
+
+def _tad_attrs(num_attrs):
+    if not 1 <= int(num_attrs) <= TAD_MAX_ATTRS:
+        raise ValueError(f"{num_attrs} attributes: the TAD kernels take 1..{TAD_MAX_ATTRS} (one packed word per row)")
+    return int(num_attrs)
+
+
+def tad_counts_shape(num_cols, num_attrs):
+    return (num_cols, TAD_THRESHOLDS, _tad_attrs(num_attrs) + 1)
+
+
+def tad_range(z, t, col_max, col_min, thr):
+    """col_max, col_min fp32 [L]: exact column maximum and minimum of z fp32 [N][L]; thr fp32 [L][11] =
+    t[k] * (col_max - col_min) + col_min, every operation rounded on its own (encdiff_tad_range).
+    t fp32 [11]: torch.arange(0.0, 1.0001, step=0.1), uploaded."""
+    N, Lc = _tad_z(z).shape
+    _dev(t, F32, (TAD_THRESHOLDS,), "t"), _dev(col_max, F32, (Lc,), "col_max"), _dev(col_min, F32, (Lc,), "col_min")
+    _dev(thr, F32, (Lc, TAD_THRESHOLDS), "thr")
+    check(lib.encdiff_tad_range(_p(z), N, Lc, _p(t), _p(col_max), _p(col_min), _p(thr), _s()), "encdiff_tad_range")
+
+
+def tad_counts(z, packed, num_attrs, thr, counts):
+    """counts int32 tad_counts_shape(L, A) (zeroed here): counts[l][k][a] = #{rows: z[row][l] >=
+    thr[l][k] and label a set}, counts[l][k][A] = #{rows: z[row][l] >= thr[l][k]}; packed int64 [N],
+    bit a of a word = label a of the row (encdiff_tad_counts)."""
+    N, Lc = _tad_z(z).shape
+    A = _tad_attrs(num_attrs)
+    _dev(packed, torch.int64, (N,), "packed"), _dev(thr, F32, (Lc, TAD_THRESHOLDS), "thr")
+    _dev(counts, torch.int32, (Lc, TAD_THRESHOLDS, A + 1), "counts")
+    check(lib.encdiff_tad_counts(_p(z), _p(packed), N, Lc, A, _p(thr), _p(counts), _s()), "encdiff_tad_counts")
+
+
+def tad_label_joint(packed, num_attrs, joint):
+    """joint int32 [A][A] (zeroed here): rows with labels i and j both set (encdiff_tad_label_joint)."""
+    A = _tad_attrs(num_attrs)
+    assert packed.dim() == 1 and packed.numel() >= 1, f"packed: (N,) expected, got {tuple(packed.shape)}"
+    _dev(packed, torch.int64, packed.shape, "packed"), _dev(joint, torch.int32, (A, A), "joint")
+    check(lib.encdiff_tad_label_joint(_p(packed), packed.numel(), A, _p(joint), _s()), "encdiff_tad_label_joint")
+
+
+def tad_auroc(counts, joint, col_max, col_min, n, aurocs):
+    """aurocs fp32 [A][L]: the larger ROC area of the classifiers z >= thr_k and z < thr_k per
+    (attribute, column) from tad_counts' counts and tad_label_joint's table over n rows; 0.5 where
+    col_max - col_min > 0.2 is false (encdiff_tad_auroc)."""
+    assert counts.dim() == 3
+    Lc, A = counts.shape[0], _tad_attrs(counts.shape[2] - 1)
+    if int(n) < 1:
+        raise ValueError(f"n={n} rows")
+    _dev(counts, torch.int32, (Lc, TAD_THRESHOLDS, A + 1), "counts"), _dev(joint, torch.int32, (A, A), "joint")
+    _dev(col_max, F32, (Lc,), "col_max"), _dev(col_min, F32, (Lc,), "col_min"), _dev(aurocs, F32, (A, Lc), "aurocs")
+    check(lib.encdiff_tad_auroc(_p(counts), _p(joint), _p(col_max), _p(col_min), int(n), Lc, A, _p(aurocs), _s()),
+          "encdiff_tad_auroc")
+
+
 # ------------------------------------------------------------------ fp32 (ENCDIFF_DT_F32) forward
 # The reference-precision forms of the same entry points (include/encdiff_hip.h "dtype"): fp32
 # activations end to end, for the fp32 parity path (unet_f32.py).

@@ -1032,6 +1032,48 @@ int encdiff_mig_hist(const float* codes, int n_rows, int dims, const int* mig_id
 int encdiff_mig_finalize(const int* counts, int dims, int num_factors, const int* factor_sizes, int m, double* mi,
                          double* h, double* score, void* stream);
 
+/* ---------------------------------------------------------------- TAD (CelebA attribute metric)
+ * The array work of celeba_tad.py / ae_utils_exp.py (aurocs_search, aurocs, calculate_auroc,
+ * LatentClass) over a device table z fp32 [n][L] (the concept tokens of a row, flattened) and the
+ * labels of a row packed into one 64-bit word, bit a = attribute a, a < A <= 64 (bits >= A are
+ * ignored).  Everything is device memory.  Integer atomics only, no floating-point atomics: a second
+ * launch gives the same bits.  Nothing is read back or allocated, so every entry point can be
+ * graph-captured; the integer outputs are zeroed by the call.
+ * Refusals, nothing is launched: a pointer NULL: ENCDIFF_ERR_ARG; n outside 1..2^31-1, L < 1 or
+ * A outside 1..64: ENCDIFF_ERR_SHAPE. */
+#define ENCDIFF_TAD_THRESHOLDS 11
+#define ENCDIFF_TAD_MAX_ATTRS 64
+#define ENCDIFF_TAD_COL_TILE 32  /* columns of one counting workgroup */
+#define ENCDIFF_TAD_ROW_STEP 512 /* rows one counting workgroup takes per pass */
+
+/* col_max, col_min fp32 [L]: the exact maximum and minimum of every column over the n rows (NaN
+ * when the column holds one); thr fp32 [L][11]: thr[l][k] = t[k] * (col_max[l] - col_min[l]) +
+ * col_min[l] in float32, the difference, the product and the sum each rounded on its own.
+ * t fp32 [11]: the thresholds, torch.arange(0.0, 1.0001, step=0.1), passed in and not recomputed. */
+int encdiff_tad_range(const float* z, long long n, int L, const float* t, float* col_max, float* col_min, float* thr,
+                      void* stream);
+
+/* counts int32 [L][11][A + 1], one pass over z:
+ *   counts[l][k][a] = #{rows : z[row][l] >= thr[l][k] and label a set}, a < A;
+ *   counts[l][k][A] = #{rows : z[row][l] >= thr[l][k]}.
+ * Each is exactly what 11 independent >= comparisons per element give (a NaN passes none). */
+int encdiff_tad_counts(const float* z, const long long* packed, long long n, int L, int A, const float* thr,
+                       int* counts, void* stream);
+
+/* joint int32 [A][A]: joint[i][j] = #{rows : labels i and j both set}; its diagonal is the number
+ * of positives of every attribute. */
+int encdiff_tad_label_joint(const long long* packed, long long n, int A, int* joint, void* stream);
+
+/* aurocs fp32 [A][L] from the counts, the joint table's diagonal P[a] and Ng[a] = n - P[a]:
+ * for the classifier z >= thr_k, fpr_k = fp_k / Ng and tpr_k = tp_k / P (float32 quotients of the
+ * counts), both sorted ascending on their own as the reference does (they fall with k: a reversal),
+ * area = sum_{i = 1..10} tpr_i * (fpr_i - fpr_{i-1}) in float32 in index order; likewise for the
+ * classifier z < thr_k (tp = P - tp_k, fp = Ng - fp_k; already ascending); the larger area.
+ * A column whose col_max - col_min > 0.2 is false keeps 0.5.  A constant attribute (P = 0 or
+ * Ng = 0) divides 0 by 0: its row is NaN where the column is not gated, as in the reference. */
+int encdiff_tad_auroc(const int* counts, const int* joint, const float* col_max, const float* col_min, long long n,
+                      int L, int A, float* aurocs, void* stream);
+
 /* Library/device information (for tests): returns the number of exported kernels. */
 int encdiff_version(void);
 
