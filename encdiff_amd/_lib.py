@@ -199,8 +199,15 @@ class SamplerStepArgs(C.Structure):
                 ("x_out", vp), ("x0_out", vp), ("idx_out", vp)]
 
 
+class ReconArgs(C.Structure):
+    _fields_ = [("a", vp), ("b", vp), ("sa", C.c_longlong * 4), ("sb", C.c_longlong * 4),
+                ("n", C.c_int), ("ch", C.c_int), ("h", C.c_int), ("w", C.c_int),
+                ("pre_add", C.c_float), ("pre_mul", C.c_float),
+                ("window", vp), ("partial", vp), ("ssim", vp), ("mse", vp)]
+
+
 _PROTOS = {
-    "encdiff_gemm": [C.POINTER(GemmArgs), vp],
+    "encdiff_gemm":[C.POINTER(GemmArgs), vp],
     "encdiff_gemm_pair": [C.POINTER(GemmArgs), C.POINTER(GemmArgs), vp],
     "encdiff_gemm_pair_ex": [C.POINTER(GemmArgs), C.POINTER(GemmArgs), C.POINTER(GemmArgs), C.c_int, vp],
     "encdiff_gemm_finalize": [C.POINTER(GemmArgs), vp],
@@ -272,6 +279,8 @@ _PROTOS = {
     "encdiff_tad_counts": [vp, vp, C.c_longlong, C.c_int, C.c_int, vp, vp, vp],
     "encdiff_tad_label_joint": [vp, C.c_longlong, C.c_int, vp, vp],
     "encdiff_tad_auroc": [vp, vp, vp, vp, C.c_longlong, C.c_int, C.c_int, vp, vp],
+    "encdiff_ssim_mse": [C.POINTER(ReconArgs), vp],
+    "encdiff_ssim_mse_workspace": [C.POINTER(ReconArgs), C.POINTER(C.c_longlong)],
     "encdiff_version": [],
 }
 

@@ -1006,6 +1006,71 @@ class LatentDiffusion(DDPM):
         return {"TAD": head, "per_attribute": res}
 
     @torch.no_grad()
+    def reconstruction_metrics(self, pool=None, images=None, ddim_steps=200, eta=1., batch_size=64, max_images=None,
+                               layout="reference", return_images=False):
+        """The loop of recon_metrics.py:73-99 on the device, in eval mode: per batch get_input (first
+        stage and concept tokens), DDIM sampling under the batch's own tokens, decode_first_stage,
+        then SSIM and MSE of the decoded images against the inputs (csrc/recon.hip), written at the
+        batch's offset into device buffers that are read back once at the end.  pool: the image pool
+        (encdiff_amd.data.ImagePool, or a uint8 (N, H, W, C) device tensor), batched in dataset order
+        as encode_dataset does; or images: float32 (N, H, W, C) in [-1, 1], as a batch['image'].
+        layout: metrics.reconstruction_views -- "reference" scores as the script does, "nchw" on
+        (B, C, H, W) planes.  Returns {"ssim", "mse": the mean of the per-batch means, as the script's
+        np.mean(ssim_score_list) (a short last batch weighs as a whole one), "per_image": {"ssim",
+        "mse"} float64 (n,), "n"}, and with return_images the scored "x0" (n, H, W, C) and "x_recon"
+        (n, C, H, W).  LPIPS (the lpips package and AlexNet weights) is not computed."""
+        from encdiff_amd import metrics
+        if (pool is None) == (images is None):
+            raise ValueError("reconstruction_metrics takes either pool or images")
+        if layout not in metrics.RECON_LAYOUTS:
+            raise ValueError(f"layout {layout!r}: one of {metrics.RECON_LAYOUTS}")
+        if batch_size < 1:
+            raise ValueError(f"batch_size={batch_size}")
+        src = images if pool is None else (pool.images if hasattr(pool, "images") else pool)
+        if src.ndim != 4:
+            raise ValueError(f"(N, H, W, C) images expected, got shape {tuple(src.shape)}")
+        if pool is not None and src.dtype != torch.uint8:
+            raise ValueError(f"an image pool holds uint8 pixels, got {src.dtype}; pass float images as images=")
+        n = src.shape[0] if max_images is None else min(src.shape[0], int(max_images))
+        if n < 1:
+            raise ValueError("no images to score")
+        dev = self.device
+        ssim = torch.empty(n, device=dev, dtype=torch.float64)
+        mse = torch.empty(n, device=dev, dtype=torch.float64)
+        order = torch.arange(n, device=dev, dtype=torch.int64) if pool is not None else None
+        kept_x0, kept_rec = [], []
+        was = self.training
+        self.eval()
+        try:
+            for s in range(0, n, batch_size):
+                b = min(batch_size, n - s)
+                if pool is not None:
+                    img = torch.empty(b, src.shape[3], src.shape[1], src.shape[2], device=dev)
+                    step = torch.zeros(1, device=dev, dtype=torch.int64)
+                    ops.gather_images_u8(src, order[s:s + b], step, b, img, advance=False)
+                    x0 = img.permute(0, 2, 3, 1)  # the batch['image'] view of the gathered NCHW images
+                else:
+                    x0 = src[s:s + b].to(dev).float()
+                _, c, _, _, _, _ = self.get_input({self.first_stage_key: x0}, self.first_stage_key,
+                                                  return_first_stage_outputs=True, force_c_encode=True,
+                                                  return_original_cond=True, bs=b, return_false=True)
+                samples, _ = self.sample_log(cond=c, batch_size=b, ddim=True, ddim_steps=ddim_steps, eta=eta)
+                x_recon = self.decode_first_stage(samples).float()
+                metrics.reconstruction_scores(x0, x_recon, layout, out_ssim=ssim[s:s + b], out_mse=mse[s:s + b])
+                if return_images:
+                    kept_x0.append(x0.contiguous().clone())
+                    kept_rec.append(x_recon.clone())
+        finally:
+            self.train(was)
+        both = torch.stack([ssim, mse]).cpu().numpy()  # the one read-back
+        means = np.array([both[:, s:s + batch_size].mean(axis=1) for s in range(0, n, batch_size)])
+        out = {"ssim": float(means[:, 0].mean()), "mse": float(means[:, 1].mean()),
+               "per_image": {"ssim": both[0].copy(), "mse": both[1].copy()}, "n": int(n)}
+        if return_images:
+            out["x0"], out["x_recon"] = torch.cat(kept_x0), torch.cat(kept_rec)
+        return out
+
+    @torch.no_grad()
     def log_images(self, batch, N=8, n_row=4, sample=True, ddim_steps=200, ddim_eta=1., return_keys=None,
                    quantize_denoised=True, inpaint=True, plot_denoise_rows=False, plot_progressive_rows=True,
                    sample_swap=False, plot_diffusion_rows=True, **kwargs):

@@ -13,6 +13,10 @@ CelebA has no factor grid; its models are scored with TAD (celeba_tad.py; ae_uti
 aurocs_search) from the 40 binary attributes: per (attribute, token column) ROC areas from integer
 counts (csrc/tad.hip), then a few hundred numbers of host arithmetic -- the last section below.
 
+Reconstruction quality is scored as recon_metrics.py scores it: SSIM (calculate_ssim, with the
+window of create_window) and MSE of decoded images against their inputs, one fused fp64 kernel
+(csrc/recon.hip) -- the section after TAD.  LPIPS is not computed.
+
 Out of scope: beta-VAE and DCI (they train sklearn classifiers) and the per-token PCA eval_func
 applies to 3-D token arrays -- the scalar codes are scored, as the reference does when it has them.
 """
@@ -333,3 +337,75 @@ def tad_score(z, targ, thresh=0.75, ent_red_thresh=0.2):
     res = tad_aurocs(z, targ)
     return tad_from_aurocs(res["aurocs"].cpu().numpy(), res["label_joint"].cpu().numpy(), int(z.shape[0]),
                            thresh=thresh, ent_red_thresh=ent_red_thresh)
+
+
+# ------------------------------------------------------------------ reconstruction scores
+SSIM_WINDOW = 11        # calculate_ssim's window_size default; fixed in the kernel (csrc/recon.hip)
+RECON_LAYOUTS = ("reference", "nchw")
+
+
+def ssim_window():
+    """The 11 x 11 float32 weights of recon_metrics.py's create_window, bit for bit: the 1-D
+    Gaussian (sigma 1.5) from Python floats, normalised in float32, and its outer product taken
+    with torch's float32 mm.  No exact product of two 1-D passes, and the sum is 0.99999993."""
+    import torch
+    from math import exp
+    sigma = 1.5
+    gauss = torch.Tensor([exp(-(x - SSIM_WINDOW // 2) ** 2 / float(2 * sigma ** 2)) for x in range(SSIM_WINDOW)])
+    col = (gauss / gauss.sum()).unsqueeze(1)
+    return col.mm(col.t()).float().contiguous()
+
+
+def _recon_pair(a, b):
+    import torch
+    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)):
+        raise ValueError("the reconstruction scores take torch tensors")
+    if a.ndim != 4 or a.shape != b.shape:
+        raise ValueError(f"two (B, Ch, H, W) batches of one shape expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if min(a.shape) < 1 or a.numel() >= 2 ** 31:
+        raise ValueError(f"batches of shape {tuple(a.shape)}: every axis >= 1 and fewer than 2^31 elements")
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise ValueError(f"float32 images expected, got {a.dtype} and {b.dtype}")
+    if not (a.is_cuda and b.is_cuda):
+        raise RuntimeError("the reconstruction scores run on the HIP device; there is no CPU fallback")
+
+
+def ssim(a, b):
+    """calculate_ssim(a, b) of the reference on the device: fp64 (B,) device tensor, the mean SSIM
+    over Ch, H, W of the float32 (B, Ch, H, W) device tensors a and b (any strides)."""
+    _recon_pair(a, b)
+    from . import ops
+    return ops.ssim_mse(a, b)[0]
+
+
+def mse(a, b):
+    """calculate_mse(a, b) of the reference on the device: fp64 (B,) device tensor."""
+    _recon_pair(a, b)
+    from . import ops
+    return ops.ssim_mse(a, b)[1]
+
+
+def reconstruction_views(x0, x_recon, layout="reference"):
+    """The two (B, Ch, H, W) views recon_metrics.py:89-95 scores, as strides over the tensors given.
+    x0: (B, H, W, C) as the data gives it; x_recon: (B, C, H, W) as decode_first_stage gives it.
+    layout "reference": the script's call, calculate_ssim(x0, x_recon.permute(0, 2, 3, 1)) -- the
+    image rows become SSIM's channels and its window slides over the (width, colour) plane, W x C.
+    layout "nchw": the textbook call on (B, C, H, W) planes, x0 permuted instead."""
+    if layout not in RECON_LAYOUTS:
+        raise ValueError(f"layout {layout!r}: one of {RECON_LAYOUTS}")
+    if x0.ndim != 4 or x_recon.ndim != 4 or tuple(x_recon.permute(0, 2, 3, 1).shape) != tuple(x0.shape):
+        raise ValueError(f"x0 (B, H, W, C) and x_recon (B, C, H, W) expected, got {tuple(x0.shape)} and "
+                         f"{tuple(x_recon.shape)}")
+    if layout == "reference":
+        return x0, x_recon.permute(0, 2, 3, 1)
+    return x0.permute(0, 3, 1, 2), x_recon
+
+
+def reconstruction_scores(x0, x_recon, layout="reference", out_ssim=None, out_mse=None):
+    """SSIM and MSE of recon_metrics.py for a batch in [-1, 1]: both tensors mapped through
+    (x + 1.) / 2. in float32 inside the kernel and scored in the layout of reconstruction_views.
+    Returns fp64 (B,) device tensors (ssim, mse), written into out_ssim / out_mse where given."""
+    a, b = reconstruction_views(x0, x_recon, layout)
+    _recon_pair(a, b)
+    from . import ops
+    return ops.ssim_mse(a, b, pre_add=1., pre_mul=0.5, out_ssim=out_ssim, out_mse=out_mse)

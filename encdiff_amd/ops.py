@@ -1664,6 +1664,64 @@ def tad_auroc(counts, joint, col_max, col_min, n, aurocs):
           "encdiff_tad_auroc")
 
 
+# ------------------------------------------------------------------ reconstruction scores
+SSIM_WINDOW = 11
+_RECON_WINDOW = {}  # device index -> the reference's 11 x 11 float32 weights, uploaded once
+
+
+def recon_args(a, b, pre_add=0., pre_mul=1.):
+    """The shape, strides, addresses and map of an encdiff_ssim_mse call on a and b, (n, ch, h, w)
+    float32 tensors of equal shape and any strides (read in place); window, workspace and outputs
+    are left to ssim_mse.  Nothing is launched: tests read the struct."""
+    assert a.dim() == 4 and a.shape == b.shape, f"(n, ch, h, w) pairs expected, got {tuple(a.shape)}, {tuple(b.shape)}"
+    assert a.dtype == F32 and b.dtype == F32, f"float32 expected, got {a.dtype}, {b.dtype}"
+    n, ch, h, w = (int(v) for v in a.shape)
+    return L.ReconArgs(a=a.data_ptr(), b=b.data_ptr(), sa=(C.c_longlong * 4)(*a.stride()),
+                       sb=(C.c_longlong * 4)(*b.stride()), n=n, ch=ch, h=h, w=w,
+                       pre_add=float(pre_add), pre_mul=float(pre_mul))
+
+
+def ssim_mse_workspace_bytes(n, ch, h, w):
+    nb = C.c_longlong(0)
+    check(lib.encdiff_ssim_mse_workspace(C.byref(L.ReconArgs(n=n, ch=ch, h=h, w=w)), C.byref(nb)),
+          "encdiff_ssim_mse_workspace")
+    return nb.value
+
+
+def _recon_window(device):
+    win = _RECON_WINDOW.get(device.index)
+    if win is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the SSIM window is first needed inside a graph capture: run ops.ssim_mse eagerly "
+                               "once (or pass window=) before capturing")
+        from .metrics import ssim_window
+        win = _RECON_WINDOW[device.index] = ssim_window().to(device)
+    return win
+
+
+def ssim_mse(a, b, pre_add=0., pre_mul=1., window=None, out_ssim=None, out_mse=None):
+    """(ssim, mse) fp64 (n,): per image the mean SSIM (11 x 11 window, zero padding 5) and the mean
+    squared difference over ch, h, w of the (n, ch, h, w) float32 device tensors a and b, taken at
+    their strides without a copy, each element first mapped to (x + pre_add) * pre_mul in float32
+    (encdiff_ssim_mse).  window: fp32 (11, 11) device weights, default metrics.ssim_window() cached
+    per device; the workspace is library scratch.  out_ssim / out_mse: contiguous fp64 (n,) device
+    views to write into (e.g. a slice of a longer buffer)."""
+    args = recon_args(a, b, pre_add, pre_mul)
+    assert a.is_cuda and b.is_cuda and a.device == b.device, "HIP device tensors required"
+    n, dev = args.n, a.device
+    window = _recon_window(dev) if window is None else _dev(window, F32, (SSIM_WINDOW, SSIM_WINDOW), "window")
+    if out_ssim is None:
+        out_ssim = torch.empty(n, device=dev, dtype=torch.float64)
+    if out_mse is None:
+        out_mse = torch.empty(n, device=dev, dtype=torch.float64)
+    _dev(out_ssim, torch.float64, (n,), "out_ssim"), _dev(out_mse, torch.float64, (n,), "out_mse")
+    nbytes = ssim_mse_workspace_bytes(args.n, args.ch, args.h, args.w)
+    ws = scratch("recon_partial", nbytes // 8, torch.float64, dev.index)
+    args.window, args.partial, args.ssim, args.mse = _p(window), _p(ws), _p(out_ssim), _p(out_mse)
+    check(lib.encdiff_ssim_mse(C.byref(args), _s()), "encdiff_ssim_mse")
+    return out_ssim, out_mse
+
+
 # ------------------------------------------------------------------ fp32 (ENCDIFF_DT_F32) forward
 # The reference-precision forms of the same entry points (include/encdiff_hip.h "dtype"): fp32
 # activations end to end, for the fp32 parity path (unet_f32.py).

@@ -1074,6 +1074,46 @@ int encdiff_tad_label_joint(const long long* packed, long long n, int A, int* jo
 int encdiff_tad_auroc(const int* counts, const int* joint, const float* col_max, const float* col_min, long long n,
                       int L, int A, float* aurocs, void* stream);
 
+/* ---------------------------------------------------------------- reconstruction scores
+ * The scoring of recon_metrics.py (calculate_ssim / _ssim / create_window, calculate_mse) of two
+ * float32 image batches a and b of n images with ch planes of h x w pixels each, read in place:
+ * element (i, c, y, x) of a lies at a[i sa[0] + c sa[1] + y sa[2] + x sa[3]] (element strides, so
+ * an NCHW tensor and a permuted view of one are both taken without a copy), likewise b with sb.
+ * The value used of an element x is (x + pre_add) * pre_mul in float32, the sum and the product
+ * each rounded on its own: (1, 0.5) is the script's (x + 1.) / 2., (0, 1) the identity.
+ *   ssim[i] = the mean over ch, h, w of ((2 mu1 mu2 + C1)(2 s12 + C2)) / ((mu1^2 + mu2^2 + C1)
+ *     (s1 + s2 + C2)), C1 = 0.01^2, C2 = 0.03^2, the five moments taken per plane under the
+ *     11 x 11 window with zero padding 5 (the padding is zero after the map: only pixels of the
+ *     plane are mapped);
+ *   mse[i] = the mean over ch, h, w of (a - b)^2.
+ * window fp32 [11][11] on the device: the reference's 2-D weights, passed in and not recomputed
+ * (they are no exact outer product and do not sum to 1).  Inputs and weights are the reference's
+ * float32 values; the moments, the map and all sums are fp64 in a fixed order with no atomics: a
+ * second launch gives the same bits.  Nothing is read back, allocated or zeroed by a memset, so
+ * the call can be graph-captured.  partial is scratch of encdiff_ssim_mse_workspace bytes, fully
+ * written before it is read.  ssim and mse take n values each and may point into longer buffers.
+ * Refusals, nothing is launched: a pointer NULL: ENCDIFF_ERR_ARG; n, ch, h or w < 1, or
+ * n * ch * h * w >= 2^31: ENCDIFF_ERR_SHAPE. */
+#define ENCDIFF_SSIM_WINDOW 11
+
+typedef struct {
+  const float* a;
+  const float* b;
+  long long sa[4], sb[4]; /* element strides of (image, channel, row, column) */
+  int n, ch, h, w;
+  float pre_add, pre_mul;
+  const float* window; /* fp32 [11][11], device */
+  double* partial;     /* workspace, device */
+  double* ssim;        /* fp64 [n], device */
+  double* mse;         /* fp64 [n], device */
+} EncdiffReconArgs;
+
+int encdiff_ssim_mse(const EncdiffReconArgs* args, void* stream);
+
+/* bytes: the size of args->partial for args' n, ch, h, w (nothing else of args is read); 16 bytes
+ * per tile of a plane. */
+int encdiff_ssim_mse_workspace(const EncdiffReconArgs* args, long long* bytes);
+
 /* Library/device information (for tests): returns the number of exported kernels. */
 int encdiff_version(void);
 
