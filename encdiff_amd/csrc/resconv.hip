@@ -594,8 +594,10 @@ int rc_plan(const EncdiffResConvArgs& a, RcPlan& q, int& tn) {
     if ((a.tile_m != 1 && a.tile_m != 2 && a.tile_m != 4) || mtg % a.tile_m) return ENCDIFF_ERR_ARG;
     q.mc = a.tile_m;
   } else {  // up to 4 tiles per workgroup, fewer while that leaves < 256 workgroups (tools/rc_bench.py
-            // --tiles at B = 8: 16x16 x 64 channels 11.6 -> 10.8 us with 2 tiles / 256 workgroups)
-    q.mc = mtg >= 4 ? 4 : mtg >= 2 ? 2 : 1;
+            // --tiles at B = 8: 16x16 x 64 channels 11.6 -> 10.8 us with 2 tiles / 256 workgroups).
+            // mc must divide mtg (12x12: 9 tiles), or the last mtg % mc tiles of a group have no
+            // workgroup; halving keeps it a divisor
+    q.mc = mtg % 4 == 0 ? 4 : mtg % 2 == 0 ? 2 : 1;
     while (q.mc > 1 && q.ngroup * (mtg / q.mc) * nslice < 256) q.mc >>= 1;
   }
   q.wk = RC_NW / q.mc;
