@@ -217,6 +217,8 @@ _PROTOS = {
     "encdiff_gemm_ex": [C.POINTER(GemmArgs), C.c_int, C.POINTER(C.c_int), vp],
     "encdiff_gemm_pair_dx": [C.POINTER(GemmArgs), C.POINTER(GemmArgs), C.POINTER(GemmArgs), C.c_int, C.c_int,
                              C.POINTER(C.c_int), vp],
+    "encdiff_gemm_check": [C.POINTER(GemmArgs), C.POINTER(C.c_int)],
+    "encdiff_gemm_tile_shape": [C.c_int] + [C.POINTER(C.c_int)] * 4,
     "encdiff_groupnorm_fwd": [C.POINTER(GroupNormArgs), vp],
     "encdiff_groupnorm_bwd": [C.POINTER(GroupNormArgs), vp],
     "encdiff_layernorm_fwd": [C.POINTER(LayerNormArgs), vp],

@@ -2148,15 +2148,26 @@ hipError_t launch_lna(const EncdiffGemmArgs& p, const GemmAux& aux, hipStream_t 
   return hipGetLastError();
 }
 
-// halo tiles: ids 16.. (tile_halo_bm / tile_halo_bn), 3-deep B ring, window + ring in dynamic LDS
+// halo tiles: ids 16..23, 3-deep B ring, window + ring in dynamic LDS
 constexpr int HALO_NS = 3;
 constexpr int HALO_LDS_MAX = 156 * 1024;  // 160 KiB less the paired kernel's static finalize scratch
-__host__ __device__ constexpr int halo_bm(int t) {
-  return t == 16 ? 64 : t == 17 ? 128 : t == 18 ? 128 : t == 19 ? 256 : t == 20 ? 128 : t == 21 ? 256 : t == 22 ? 64 : 64;
-}
-__host__ __device__ constexpr int halo_bn(int t) {
-  return t == 16 ? 64 : t == 17 ? 64 : t == 18 ? 128 : t == 19 ? 32 : t == 20 ? 32 : t == 21 ? 64 : t == 22 ? 128 : 32;
-}
+
+// EncdiffGemmArgs.tile -> the shape of the single-GEMM tile kernel, stated ONCE: the dispatch
+// (launch_tile), the halo geometry, the ln_y check and encdiff_gemm_tile_shape all read it.
+// Ids without a row (bm == 0) are no tile shapes: 32-34 / 36 name the WG3 / WGL kernels.
+struct TileDims { int bm, bn, kb, ns; };
+constexpr int TILE_IDS = 24;
+constexpr TileDims TILES[TILE_IDS] = {
+    {},                                                                      // 0: auto (pick_tile)
+    {128, 128, BK, 2}, {128, 64, BK, 2}, {64, 128, BK, 2}, {64, 64, BK, 2},  // 1-4: ring tiles
+    {64, 64, BK, 4}, {64, 128, BK, 3}, {64, 64, 128, 2}, {64, 128, 128, 2},  // 5-8
+    {64, 64, BK, 6}, {64, 64, BK, 8},                                        // 9, 10
+    {}, {}, {}, {}, {},                                                      // 11-15
+    {64, 64, BK, HALO_NS}, {128, 64, BK, HALO_NS}, {128, 128, BK, HALO_NS}, {256, 32, BK, HALO_NS},  // 16-19: halo tiles
+    {128, 32, BK, HALO_NS}, {256, 64, BK, HALO_NS}, {64, 128, BK, HALO_NS}, {64, 32, BK, HALO_NS},   // 20-23
+};
+constexpr bool is_tile(int t) { return t > 0 && t < TILE_IDS && TILES[t].bm != 0; }
+
 inline size_t halo_lds_bytes(const HaloGeom& h, int bm, int bn) {
   const size_t win = (size_t)h.chunks * 16 + (size_t)HALO_NS * bn * BK * 2;
   const size_t epi = (size_t)bm * (bn + 4) * 4;
@@ -2174,17 +2185,30 @@ hipError_t launch_halo_t(const EncdiffGemmArgs& p, const GemmAux& aux, hipStream
   return hipGetLastError();
 }
 
+// the tile kernel of id T (a row of TILES) on operand modes AM x BMD (halo tiles: A_HALO x BMD)
+template <int T, int AM, int BMD>
+hipError_t launch_tile(const EncdiffGemmArgs& p, const GemmAux& aux, hipStream_t s) {
+  constexpr TileDims t = TILES[T];
+  static_assert(is_tile(T), "tile id without a shape");
+  if constexpr (T >= 16) {
+    static_assert(t.kb == BK && t.ns == HALO_NS, "halo tiles: one stage depth, one ring depth");
+    return launch_halo_t<t.bm, t.bn, BMD>(p, aux, s);
+  } else {
+    return launch_t<t.bm, t.bn, AM, BMD, t.ns, t.kb>(p, aux, s);
+  }
+}
+
 template <int BMD>
 hipError_t launch_halo(const EncdiffGemmArgs& p, const GemmAux& aux, int tile, hipStream_t s) {
   switch (tile) {
-    case 16: return launch_halo_t<64, 64, BMD>(p, aux, s);
-    case 17: return launch_halo_t<128, 64, BMD>(p, aux, s);
-    case 18: return launch_halo_t<128, 128, BMD>(p, aux, s);
-    case 19: return launch_halo_t<256, 32, BMD>(p, aux, s);
-    case 20: return launch_halo_t<128, 32, BMD>(p, aux, s);
-    case 21: return launch_halo_t<256, 64, BMD>(p, aux, s);
-    case 22: return launch_halo_t<64, 128, BMD>(p, aux, s);
-    default: return launch_halo_t<64, 32, BMD>(p, aux, s);
+    case 16: return launch_tile<16, A_HALO, BMD>(p, aux, s);
+    case 17: return launch_tile<17, A_HALO, BMD>(p, aux, s);
+    case 18: return launch_tile<18, A_HALO, BMD>(p, aux, s);
+    case 19: return launch_tile<19, A_HALO, BMD>(p, aux, s);
+    case 20: return launch_tile<20, A_HALO, BMD>(p, aux, s);
+    case 21: return launch_tile<21, A_HALO, BMD>(p, aux, s);
+    case 22: return launch_tile<22, A_HALO, BMD>(p, aux, s);
+    default: return launch_tile<23, A_HALO, BMD>(p, aux, s);
   }
 }
 
@@ -2194,16 +2218,16 @@ hipError_t launch_modes(const EncdiffGemmArgs& p, const GemmAux& aux, int tile, 
     if (tile >= 16) return launch_halo<BMD>(p, aux, tile, s);
   }
   switch (tile) {
-    case 1: return launch_t<128, 128, AM, BMD>(p, aux, s);
-    case 2: return launch_t<128, 64, AM, BMD>(p, aux, s);
-    case 3: return launch_t<64, 128, AM, BMD>(p, aux, s);
-    case 5: return launch_t<64, 64, AM, BMD, 4>(p, aux, s);
-    case 6: return launch_t<64, 128, AM, BMD, 3>(p, aux, s);
-    case 7: return launch_t<64, 64, AM, BMD, 2, 128>(p, aux, s);
-    case 8: return launch_t<64, 128, AM, BMD, 2, 128>(p, aux, s);
-    case 9: return launch_t<64, 64, AM, BMD, 6>(p, aux, s);
-    case 10: return launch_t<64, 64, AM, BMD, 8>(p, aux, s);
-    default: return launch_t<64, 64, AM, BMD>(p, aux, s);
+    case 1: return launch_tile<1, AM, BMD>(p, aux, s);
+    case 2: return launch_tile<2, AM, BMD>(p, aux, s);
+    case 3: return launch_tile<3, AM, BMD>(p, aux, s);
+    case 5: return launch_tile<5, AM, BMD>(p, aux, s);
+    case 6: return launch_tile<6, AM, BMD>(p, aux, s);
+    case 7: return launch_tile<7, AM, BMD>(p, aux, s);
+    case 8: return launch_tile<8, AM, BMD>(p, aux, s);
+    case 9: return launch_tile<9, AM, BMD>(p, aux, s);
+    case 10: return launch_tile<10, AM, BMD>(p, aux, s);
+    default: return launch_tile<4, AM, BMD>(p, aux, s);
   }
 }
 
@@ -2245,7 +2269,7 @@ int prepare_halo(const EncdiffGemmArgs& p, int tile, HaloGeom& h) {
   if (p.c_mode == ENCDIFF_OUT_F32_ATOMIC || p.c_mode == ENCDIFF_OUT_F32_ATOMIC_CONVW) return ENCDIFF_ERR_UNSUPPORTED;
   // split-K: each split stages and contracts its own slice of the source channels (gemm_tile)
   if (p.split_k > 1 && (p.conv.cin % (64 * p.split_k) || p.K % 64)) return ENCDIFF_ERR_SHAPE;
-  const int bm = halo_bm(tile), bn = halo_bn(tile);
+  const int bm = TILES[tile].bm, bn = TILES[tile].bn;
   const int H = p.conv.h, W = p.conv.w, HW = H * W, cin = p.conv.cin;
   if ((long)p.M != (long)p.conv.batch * HW || p.M % bm || bm % W || (HW % bm && bm % HW)) return ENCDIFF_ERR_SHAPE;
   const bool up = rs == ENCDIFF_RESAMPLE_UP2, s2 = rs == ENCDIFF_RESAMPLE_STRIDE2, k4 = rs == ENCDIFF_RESAMPLE_K4S2;
@@ -2349,7 +2373,7 @@ int prepare(const EncdiffGemmArgs* pa, GemmPlan& g) {
   if (p.gn_stats && (p.c_mode != ENCDIFF_OUT_BF16 || p.split_k != 1 || p.M % 64 || p.ld_gn_stats < p.N))
     return ENCDIFF_ERR_ARG;
   if (p.ln_y) {  // the tile must span every column: N <= BN, 8-column vectors
-    const int bn = (p.tile == 1 || p.tile == 3 || p.tile == 6 || p.tile == 8) ? 128 : 64;
+    const int bn = p.tile < 16 && is_tile(p.tile) ? TILES[p.tile].bn : 64;  // ring tiles; any other id counts as 64 wide
     if (p.c_mode != ENCDIFF_OUT_BF16 || p.split_k != 1 || !p.tile || p.N > bn || p.N % 8 || p.ld_ln_y % 8 ||
         !p.ln_gamma || !p.ln_beta || !p.ln_stats)
       return ENCDIFF_ERR_ARG;
@@ -3027,6 +3051,22 @@ extern "C" int encdiff_gemm_finalize(const EncdiffGemmArgs* args, void* stream) 
   if (!g.ws_path || g.fold) return ENCDIFF_OK;  // folded GEMMs combined their slabs in the kernel
   const hipError_t e = launch_finalize(g.user, (hipStream_t)stream);
   return e != hipSuccess ? ENCDIFF_ERR_LAUNCH - (int)e : ENCDIFF_OK;
+}
+
+extern "C" int encdiff_gemm_check(const EncdiffGemmArgs* pa, int* tile) {
+  GemmPlan g;
+  const int rc = prepare(pa, g);
+  if (rc == ENCDIFF_OK && tile) *tile = g.tile;
+  return rc;
+}
+
+extern "C" int encdiff_gemm_tile_shape(int tile, int* bm, int* bn, int* kb, int* stages) {
+  if (!is_tile(tile)) return ENCDIFF_ERR_UNSUPPORTED;
+  if (bm) *bm = TILES[tile].bm;
+  if (bn) *bn = TILES[tile].bn;
+  if (kb) *kb = TILES[tile].kb;
+  if (stages) *stages = TILES[tile].ns;
+  return ENCDIFF_OK;
 }
 
 extern "C" int encdiff_version(void) { return 1; }

@@ -8,6 +8,7 @@ captured into a HIP graph.  Activations are 2-D [rows][channels] bf16 views
 from __future__ import annotations
 
 import ctypes as C
+import json
 import math
 import os
 from dataclasses import dataclass
@@ -65,7 +66,6 @@ WS_HALF = WS_FLOATS // 2
 STWG_WS_FLOATS = 24 * 1024 * 1024    # 96 MB (c = 64 / 128 at B = 128: 42 MB; larger batches: longer chunks)
 COUNTERS = 1 << 16                   # split-K tickets per device (one int per output tile)
 _TILES = None
-_TILE_SHAPES = {1: (128, 128), 2: (128, 64), 3: (64, 128), 4: (64, 64)}
 
 
 def scratch(name, numel, dtype=torch.float32, device=None):
@@ -109,8 +109,6 @@ def _workspace(device=None):
 def _tile_table():
     global _TILES
     if _TILES is None:
-        import json
-        import os
         path = os.environ.get("ENCDIFF_GEMM_TILES") or os.path.join(os.path.dirname(os.path.abspath(__file__)),
                                                                     "gemm_tiles.json")
         _TILES = json.load(open(path)) if os.path.exists(path) else {}
@@ -121,33 +119,51 @@ MAX_SPLIT = int(os.environ.get("ENCDIFF_MAX_SPLIT", "1024"))  # experiment knob:
 FORCE_TILE = 0  # tests: override the planned tile of every GEMM that does not pass one
 
 
+# Which (tile, split_k) plans are legal for a GEMM is decided in ONE place, the library's launch
+# validation (gemm.hip prepare()), asked through encdiff_gemm_check -- host arithmetic, no HIP call.
+# This module owns the policy only: table lookup, split heuristics, workspace capacity.
+WG3_TILES = (32, 33, 34)  # ids of the 3x3 conv weight-gradient kernel (WG3): kernels, not tile shapes
+WGL_TILE = 36             # id of the linear weight-gradient kernel (WGL)
+_WS_STANDIN = 1 << 12     # workspace address of a plan being checked: aligned as the real one, never read
+
+
+def _tile_dims():
+    """tile id -> (BM, BN, KB, ring depth) of every ring / halo tile, as gemm.hip states them."""
+    dims = {}
+    for t in range(1, 32):
+        v = [C.c_int() for _ in range(4)]
+        if lib.encdiff_gemm_tile_shape(t, *(C.byref(x) for x in v)) == 0:
+            dims[t] = tuple(x.value for x in v)
+    return dims
+
+
+_TILE_DIMS = _tile_dims()
 # halo tiles (gemm.hip tiles 16-23): BM x BN, window staged once per workgroup
-HALO_TILES = {16: (64, 64), 17: (128, 64), 18: (128, 128), 19: (256, 32), 20: (128, 32), 21: (256, 64),
-              22: (64, 128), 23: (64, 32)}
-HALO_LDS_MAX = 156 * 1024  # gemm.hip: 160 KiB less the paired kernel's static scratch
+HALO_TILES = {t: d[:2] for t, d in _TILE_DIMS.items() if t >= 16}
 
 
-def halo_fits(tile, batch, h, w, cin, resample, split=1):
-    """Host mirror of gemm.hip prepare_halo's geometry checks: the tile's BM pixels are whole
-    rows of one image (or whole images) and window + 3-deep B ring + epilogue fit the LDS.
-    split > 1: split-K by source-channel slices (cin / split channels per split, 64 | slice)."""
-    if tile not in HALO_TILES or cin % 8 or resample not in (0, 2, 3, 4):
+def _plan_ok(args, tile, split, ws_offset=0) -> bool:
+    """Whether the library launches the GEMM `args` on (tile, split) -- e.g. a table entry, measured
+    on some geometry, on THIS problem: keys carry (M, N, K, h) but not the batch, strides or
+    alignment.  Writes the candidate plan into `args` (the workspace a stand-in: nothing is
+    allocated) and asks the launch validation itself."""
+    args.tile, args.split_k = tile, split
+    args.workspace = _WS_STANDIN + 4 * ws_offset if split > 1 else None
+    return lib.encdiff_gemm_check(C.byref(args), None) == 0
+
+
+def halo_fits(tile, batch, h, w, cin, resample, split=1, b_mode=L.OPB_ROWK, c_mode=L.OUT_BF16):
+    """Whether the library accepts halo tile `tile` with `split` for the conv forward (b_mode
+    OPB_CONV_DGRAD: the 3x3 input gradient) of this geometry: the tile's BM pixels are whole rows
+    of one image (or whole images) and window + 3-deep B ring + epilogue fit the LDS; split > 1:
+    split-K by source-channel slices (cin / split channels per split, 64 | slice)."""
+    if tile not in HALO_TILES:
         return False
-    if split > 1:
-        if cin % (64 * split):
-            return False
-        cin //= split
-    bm, bn = HALO_TILES[tile]
-    hw = h * w
-    if (batch * hw) % bm or bm % w or (hw % bm and bm % hw) or (resample == 2 and (h | w) & 1):
-        return False
-    s = 2 if resample in (3, 4) else 1
-    kt = 4 if resample == 4 else 3
-    rows = min(h, bm // w)
-    ni = bm // hw if bm > hw else 1
-    npix = ni * (s * (rows - 1) + kt) * (s * (w - 1) + kt)
-    chunks = (npix * (cin // 8) + 255) & ~255
-    return max(chunks * 16 + 3 * bn * 64 * 2, bm * (bn + 4) * 4) <= HALO_LDS_MAX
+    taps = {L.RESAMPLE_K4S2: 16, L.RESAMPLE_K4S2_T: 16, L.RESAMPLE_K4S2_TP: 4}.get(resample, 9)
+    conv = L.ConvGeom(batch=batch, h=h, w=w, cin=cin, resample=resample, ld_src=cin)
+    args = L.GemmArgs(M=batch * h * w, N=64, K=taps * cin, a_mode=L.OPA_IM2COL, b_mode=b_mode, c_mode=c_mode,
+                      ldb=taps * cin, ldc=64, conv=conv, conv_cout=cin, alpha=1.0)
+    return _plan_ok(args, tile, split)
 
 
 def plan_key(M, N, K, a_mode, b_mode, c_mode, resample=0, h=0):
@@ -214,30 +230,25 @@ WG3_SPLIT = 0  # experiments: force the WG3 split
 
 def wg3_split(batch, h, w, cout, cin, resample, lda, ld_src, c_mode, tile=None):
     """Pixel chunks (split) of a 3x3 conv weight gradient on gemm.hip's WG3 kernel, or None when
-    the problem is not eligible (mirror of gemm.hip wg3_check).  A workgroup owns 32 couts x 16
-    cins x 9 taps of one chunk of whole images; its 4 (tile 32) or 8 (tile 33) waves split the
-    chunk's 32-pixel stages: the largest power-of-two split whose waves still run >= 32 / waves
-    stages and whose grid stays within 2 (4-wave) or 1 (8-wave) workgroups per CU, so the fp32
-    partial slabs stay few."""
+    the library does not take the problem on that kernel (encdiff_gemm_check decides; operands
+    16-byte aligned).  A workgroup owns 32 couts x 16 cins x 9 taps of one chunk of whole images;
+    its 4 (tile 32) or 8 (tile 33) waves split the chunk's 32-pixel stages: the largest
+    power-of-two split the library accepts whose waves still run >= 32 / waves stages and whose
+    grid stays within 2 (4-wave) or 1 (8-wave) workgroups per CU, so the fp32 partial slabs stay
+    few."""
     tile = tile or WG3_TILE
     waves = 8 if tile == 33 else 4
-    if (resample not in (L.RESAMPLE_NONE, L.RESAMPLE_UP2) or h != w or h not in (4, 8, 16) or cout % 32 or cin % 16
-            or lda % 8 or ld_src % 8 or c_mode not in (L.OUT_F32, L.OUT_F32_ACCUM)):
-        return None
-    ni = 1 if h == 16 else 2
-    rows = 4 if h == 4 else 2
-
-    def stages(p):  # 32-pixel stages per chunk
-        return (batch // p // ni) * (h // rows) if batch % (p * ni) == 0 else 0
-    if not stages(1) or stages(1) % waves:
-        return None
+    K = batch * h * w
+    args = L.GemmArgs(M=cout, N=9 * cin, K=K, a_mode=L.OPA_ROWM, b_mode=L.OPB_IM2COL, c_mode=c_mode, lda=lda,
+                      ldc=9 * cin, alpha=1.0,
+                      conv=L.ConvGeom(batch=batch, h=h, w=w, cin=cin, resample=resample, ld_src=ld_src))
     nparts = (cout // 32) * (cin // 16)
     best, p = None, 1
-    while stages(p) and stages(p) % waves == 0:
-        if stages(p) // waves >= 32 // waves and nparts * p <= 256 * (2 if waves == 4 else 1):
+    while _plan_ok(args, tile, p):
+        if K // (32 * p) // waves >= 32 // waves and nparts * p <= 256 * (2 if waves == 4 else 1):
             best = p
         p *= 2
-    return best or 1
+    return (best or 1) if p > 1 else None  # p == 1: not even the whole problem is accepted
 
 
 # tuned table entries for weight gradients over the WG3 / WGL heuristics (gemm_args): 0 off, 1 entries
@@ -250,39 +261,21 @@ WGL = int(os.environ.get("ENCDIFF_WGL", "1"))
 
 def wgl_split(M, N, K, lda, ldb, c_mode):
     """Token chunks (split) of a linear weight gradient dW[M][N] += dY^T x on gemm.hip's WGL kernel
-    (tile 36), or None when not eligible (mirror of gemm.hip wgl_check): workgroups own 64 x 64
-    output parts, their 4 waves a quarter of a chunk each in 32-token stages; the largest
-    power-of-two split whose waves still run >= 2 stages and whose grid stays <= 256 workgroups."""
-    if M % 64 or N % 64 or lda % 8 or ldb % 8 or c_mode not in (L.OUT_F32, L.OUT_F32_ACCUM) or K % 256:
+    (tile 36), or None when the library does not take the problem on that kernel (encdiff_gemm_check
+    decides; operands 16-byte aligned) or K % 256: workgroups own 64 x 64 output parts, their 4 waves
+    a quarter of a chunk each in 32-token stages; the largest power-of-two split the library accepts
+    whose waves still run >= 2 stages and whose grid stays <= 256 workgroups."""
+    if K % 256:
         return None
+    args = L.GemmArgs(M=M, N=N, K=K, a_mode=L.OPA_ROWM, b_mode=L.OPB_ROWN, c_mode=c_mode, lda=lda, ldb=ldb, ldc=N,
+                      alpha=1.0)
     parts = (M // 64) * (N // 64)
     best, p = None, 1
-    while K % (p * 128) == 0:
+    while _plan_ok(args, WGL_TILE, p):
         if K // (p * 128) >= 2 and parts * p <= 256:
             best = p
         p *= 2
     return best
-
-
-def _plan_ok(tile, split, M, N, K, c_mode, conv, lda, ldb, a_mode=None) -> bool:
-    """Whether a (tile, split) plan -- a table entry measured on some geometry -- is valid for THIS
-    problem: halo tiles need the conv's window to fit (halo_fits), WG3 / WGL tiles their kernel's
-    eligibility and a chunking that divides (wg3_check / wgl_check on the device side would raise
-    ENCDIFF_ERR_SHAPE).  Keys carry (M, N, K, h) but not the batch, strides or alignment."""
-    if tile in HALO_TILES:
-        return (conv is not None and a_mode == L.OPA_IM2COL and
-                halo_fits(tile, conv.batch, conv.h, conv.w, conv.cin, conv.resample, split))
-    if tile in (32, 33, 34):
-        if conv is None or wg3_split(conv.batch, conv.h, conv.w, M, conv.cin, conv.resample, lda, conv.ld_src,
-                                     c_mode, tile=tile) is None:
-            return False
-        ni, rows = (1 if conv.h == 16 else 2), (4 if conv.h == 4 else 2)
-        if conv.batch % (split * ni):
-            return False
-        return ((conv.batch // split // ni) * (conv.h // rows)) % (8 if tile == 33 else 4) == 0
-    if tile == 36:
-        return wgl_split(M, N, K, lda, ldb, c_mode) is not None and K % (split * 128) == 0
-    return True
 
 
 def gemm_args(M, N, K, a, lda, b, ldb, c, ldc, *, a_mode=L.OPA_ROWK, b_mode=L.OPB_ROWK, c_mode=L.OUT_BF16,
@@ -299,16 +292,31 @@ def gemm_args(M, N, K, a, lda, b, ldb, c, ldc, *, a_mode=L.OPA_ROWK, b_mode=L.OP
         tile, split_k = 4, 1
     if _WG_WHOLE:  # a WgradGroup member: whole problem, the group picks the body
         split_k = 1
+    # the problem as it will be launched; the plan (tile, split_k, workspace, split_counters) is filled
+    # in below, candidates (_plan_ok) and then the choice
+    args = L.GemmArgs(M=M, N=N, K=K, a_mode=a_mode, b_mode=b_mode, c_mode=c_mode,
+                      a=_p(a), lda=lda, b=_p(b), ldb=ldb, c=_p(c), ldc=ldc,
+                      conv=conv if conv is not None else L.ConvGeom(),
+                      conv_cout=conv_cout, convw_cin=convw_cin, alpha=alpha,
+                      bias=_p(bias), resid=_p(resid), ld_resid=ld_resid, bias_grad=_p(bias_grad),
+                      aux=_p(aux), ld_aux=ld_aux,
+                      gn_stats=_p(gn_stats), ld_gn_stats=_ld(gn_stats) if gn_stats is not None else 0,
+                      **({} if ln is None else dict(ln_gamma=_p(ln[0]), ln_beta=_p(ln[1]), ln_y=_p(ln[2]),
+                                                    ld_ln_y=_ld(ln[2]), ln_stats=_p(ln[3]), ln_eps=ln[4])),
+                      **({} if agn is None else dict(agn_gamma=_p(agn[0]), agn_beta=_p(agn[1]), agn_film=_p(agn[2]),
+                                                     ld_agn_film=_ld(agn[2]) if agn[2] is not None else 0,
+                                                     agn_eps=agn[3], agn_silu=int(agn[4]))),
+                      **({} if lna is None else dict(lna_gamma=_p(lna[0]), lna_beta=_p(lna[1]), lna_eps=lna[2])))
     if TABLE_WG and tile == 0 and split_k is None and a_mode == L.OPA_ROWM:
         # a tuned table entry for this exact weight gradient (conv: keyed with its geometry) overrides
         # the WG3 / WGL split heuristics (1: entries naming those kernels, 2: any entry)
         im2 = conv is not None and b_mode == L.OPB_IM2COL
         hit = _tile_table().get(plan_key(M, N, K, a_mode, b_mode, c_mode, conv.resample if im2 else 0,
                                          conv.h if im2 else 0))
-        if hit is not None and (TABLE_WG == 2 or int(hit[0]) in (32, 33, 34, 36)):
+        if hit is not None and (TABLE_WG == 2 or int(hit[0]) in WG3_TILES or int(hit[0]) == WGL_TILE):
             t, sp = int(hit[0]), int(hit[1])
-            if ((t not in (32, 33, 34) or WG3) and (t != 36 or WGL) and (sp == 1 or sp * M * (N + 1) <= WS_HALF // 2)
-                    and _plan_ok(t, sp, M, N, K, c_mode, conv, lda, ldb, a_mode)):
+            if ((t not in WG3_TILES or WG3) and (t != WGL_TILE or WGL) and
+                    (sp == 1 or sp * M * (N + 1) <= WS_HALF // 2) and _plan_ok(args, t, sp, ws_offset)):
                 tile, split_k = t, sp
     if (WG3 and tile == 0 and split_k is None and a_mode == L.OPA_ROWM and b_mode == L.OPB_IM2COL and
             conv is not None and N == 9 * conv.cin and K == conv.batch * conv.h * conv.w):
@@ -322,14 +330,16 @@ def gemm_args(M, N, K, a, lda, b, ldb, c, ldc, *, a_mode=L.OPA_ROWK, b_mode=L.OP
     if WGL and tile == 0 and split_k is None and a_mode == L.OPA_ROWM and b_mode == L.OPB_ROWN and (WGL == 2 or M == N):
         sp = wgl_split(M, N, K, lda, ldb, c_mode)
         if sp is not None and (sp == 1 or sp * M * (N + 1) <= WS_HALF // 2):
-            tile, split_k = 36, sp
+            tile, split_k = WGL_TILE, sp
     pm = plan_m or M  # the row count whose measured plan is used (linear_fwd plan_m)
     rs = conv.resample if conv is not None else 0
     hk = conv.h if conv is not None and (a_mode == L.OPA_IM2COL or b_mode == L.OPB_IM2COL) else 0
     if split_k is None or tile == 0:
         t, sp = plan(pm, N, K, a_mode, b_mode, c_mode, rs, hk)
-        if ((t in (32, 33, 34) and not WG3) or (t == 36 and not WGL) or  # kernel switched off, or a table
-                not _plan_ok(t, sp, M, N, K, c_mode, conv, lda, ldb, a_mode)):  # plan invalid here: generic plan
+        # kernel switched off, or the library refuses the plan here (a table entry measured on another
+        # geometry), with the tile / split the caller pinned in place of the plan's: generic plan
+        if ((t in WG3_TILES and not WG3) or (t == WGL_TILE and not WGL) or
+                not _plan_ok(args, tile or t, split_k or sp, ws_offset)):
             t, sp = plan(pm, N, K, a_mode, b_mode, c_mode, rs, hk, table=False)
         tile = tile or FORCE_TILE or t
         split_k = split_k or sp
@@ -344,20 +354,10 @@ def gemm_args(M, N, K, a, lda, b, ldb, c, ldc, *, a_mode=L.OPA_ROWK, b_mode=L.OP
         if (a_mode != L.OPA_ROWM and math.ceil(M / 32) * math.ceil(N / 32) <= COUNTERS and
                 (fold or fold_choice(pm, N, K, a_mode, b_mode, c_mode, rs, hk))):
             cnt = _counters()
-    return L.GemmArgs(M=M, N=N, K=K, a_mode=a_mode, b_mode=b_mode, c_mode=c_mode,
-                      a=_p(a), lda=lda, b=_p(b), ldb=ldb, c=_p(c), ldc=ldc,
-                      conv=conv if conv is not None else L.ConvGeom(),
-                      conv_cout=conv_cout, convw_cin=convw_cin, alpha=alpha, split_k=split_k,
-                      bias=_p(bias), resid=_p(resid), ld_resid=ld_resid, bias_grad=_p(bias_grad), tile=tile,
-                      workspace=None if ws is None else ws.data_ptr() + 4 * ws_offset, aux=_p(aux), ld_aux=ld_aux,
-                      gn_stats=_p(gn_stats), ld_gn_stats=_ld(gn_stats) if gn_stats is not None else 0,
-                      split_counters=None if cnt is None else cnt.data_ptr(),
-                      **({} if ln is None else dict(ln_gamma=_p(ln[0]), ln_beta=_p(ln[1]), ln_y=_p(ln[2]),
-                                                    ld_ln_y=_ld(ln[2]), ln_stats=_p(ln[3]), ln_eps=ln[4])),
-                      **({} if agn is None else dict(agn_gamma=_p(agn[0]), agn_beta=_p(agn[1]), agn_film=_p(agn[2]),
-                                                     ld_agn_film=_ld(agn[2]) if agn[2] is not None else 0,
-                                                     agn_eps=agn[3], agn_silu=int(agn[4]))),
-                      **({} if lna is None else dict(lna_gamma=_p(lna[0]), lna_beta=_p(lna[1]), lna_eps=lna[2])))
+    args.tile, args.split_k = tile, split_k
+    args.workspace = None if ws is None else ws.data_ptr() + 4 * ws_offset
+    args.split_counters = None if cnt is None else cnt.data_ptr()
+    return args
 
 
 def ws_floats(args) -> int:
@@ -574,7 +574,6 @@ def linear_fwd(x, w, out, bias=None, resid=None, alpha=1.0, out_f32=False, gn_st
 # LayerNorm in the producing GEMM's epilogue when one tile spans the row (N <= 128):
 # attention.py norm1/2/3 after proj_in / to_out.  ENCDIFF_LN_FUSED=0: separate kernel.
 LN_FUSED = os.environ.get("ENCDIFF_LN_FUSED", "1") != "0"
-_TILE_BN = {1: 128, 2: 64, 3: 128, 4: 64, 5: 64, 6: 128, 7: 64, 8: 128}
 
 
 def linear_fwd_ln(x, w, out, gamma, beta, y, stats, eps, bias=None, resid=None):
@@ -595,7 +594,7 @@ def linear_fwd_ln(x, w, out, gamma, beta, y, stats, eps, bias=None, resid=None):
             layernorm_fwd(out, gamma, beta, y, stats, eps)
             return
         tile = 3 if N > 64 else 4
-    elif _TILE_BN.get(tile, 64) < N:  # at training batch sizes forcing a wider tile measured slower
+    elif _TILE_DIMS.get(tile, (64, 64))[1] < N:  # at training batch sizes forcing a wider tile measured slower
         linear_fwd(x, w, out, bias=bias, resid=resid)
         layernorm_fwd(out, gamma, beta, y, stats, eps)
         return
@@ -1503,7 +1502,6 @@ def encoder_warp_fwd(u, params, unit_stride, units, context_dim, out):
 
 
 _WARP_SCRATCH = {}
-_RETIRED = []  # outgrown scratch stays allocated: graphs captured earlier still address it
 
 
 def encoder_warp_bwd(u, params, unit_stride, units, context_dim, dout, du, grads):

@@ -241,6 +241,19 @@ int encdiff_gemm_finalize(const EncdiffGemmArgs* args, void* stream);
  * Replaces the same nn.Conv2d / nn.Linear forward as encdiff_gemm. */
 int encdiff_gemm_ex(const EncdiffGemmArgs* args, int defer_finalize, int* planned, void* stream);
 
+/* Host-only: the validation encdiff_gemm runs before it launches, and nothing else -- no HIP call,
+ * no launch, no operand pointer dereferenced (pointers count for their NULL-ness and alignment
+ * only).  Returns the code the launch of `args` would return (ENCDIFF_OK / ERR_ARG / ERR_SHAPE /
+ * ERR_UNSUPPORTED) and, on ENCDIFF_OK, writes the tile the launch would run to *tile (args->tile,
+ * or the library's default when that is 0); tile may be NULL.  The ONE statement of which
+ * (tile, split_k) plans are legal for a problem: planners ask here instead of restating the rules. */
+int encdiff_gemm_check(const EncdiffGemmArgs* args, int* tile);
+
+/* Host-only: the shape of tile id `tile` -- BM x BN output tile, k-stage depth KB, LDS ring depth
+ * -- for the ring tiles 1-10 and the halo tiles 16-23 (each out-pointer may be NULL).  Every other
+ * id is ENCDIFF_ERR_UNSUPPORTED: 32-34 and 36 name the WG3 / WGL kernels, not tile shapes. */
+int encdiff_gemm_tile_shape(int tile, int* bm, int* bn, int* kb, int* stages);
+
 /* ---------------------------------------------------------------- GroupNorm
  * y = act( GN(x) * (1 + scale[b,c]) + shift[b,c] )
  * Replaces GroupNorm32 + SiLU (+ FiLM) of ResBlock in/out_layers and UNet.out

@@ -3,9 +3,10 @@ data in fp64 the restatement must EQUAL F.conv2d (every resample expressed as te
 test_conv3x3 / test_conv_halo_tiles / test_conv4x4s2 express it) and autograd's input / weight
 gradients of the same convs and of linear layers, so that a wrong reference cannot make a wrong
 kernel pass.  Operands sit as strided views inside NaN-filled buffers: the restatement reads only
-the logical operand.  The copies of the launch arithmetic are held against the library's host
-mirrors (ops.halo_fits, ops.wg3_split, ops.wgl_split) where they overlap, and against values
-worked out by hand."""
+the logical operand.  The copies of the launch arithmetic are held against the library itself --
+encdiff_gemm_check / encdiff_gemm_tile_shape, host-only queries that need no GPU, and the planner
+functions that ask them (ops.halo_fits, ops.wg3_split, ops.wgl_split) -- where they overlap, and
+against values worked out by hand."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -229,25 +230,86 @@ def test_split_ktiles_by_hand():
     assert G.tile_shape(9) == (64, 64, 64, 6) and G.tile_shape(8) == (64, 128, 128, 2) and G.tile_shape(19) == (256, 32, 64, 3)
 
 
+WS = 1 << 12    # fake split-K workspace address (aligned; encdiff_gemm_check dereferences nothing)
+PTR = 1 << 20   # fake operand address
+
+
+def lib_check(tile, split, M, N, K, a_mode, b_mode, c_mode, conv=None, *, lda=0, ldb=0, ldc=0, conv_cout=0,
+              pa=None, pb=None, pc=None, ws=WS, **kw):
+    """encdiff_gemm_check (the validation encdiff_gemm runs before it launches, host arithmetic only)
+    on a problem with null or fake pointers: (return code, tile the launch would run)."""
+    import ctypes as C
+    import encdiff_amd._lib as L
+    cg = L.ConvGeom() if conv is None else L.ConvGeom(batch=conv.batch, h=conv.h, w=conv.w, cin=conv.cin,
+                                                      resample=conv.resample, ld_src=conv.ld_src)
+    args = L.GemmArgs(M=M, N=N, K=K, a_mode=a_mode, b_mode=b_mode, c_mode=c_mode, a=pa, lda=lda, b=pb, ldb=ldb, c=pc,
+                      ldc=ldc, conv=cg, conv_cout=conv_cout, alpha=1.0, split_k=split, tile=tile,
+                      workspace=ws if split > 1 else None, **kw)
+    t = C.c_int(0)
+    rc = L.lib.encdiff_gemm_check(C.byref(args), C.byref(t))
+    return rc, t.value
+
+
+def lib_halo(tile, b, h, w, cin, rs, split=1, b_mode=G.OPB_ROWK, c_mode=G.OUT_BF16):
+    T = G.taps(rs)[0]
+    rc, _ = lib_check(tile, split, b * h * w, 64, T * cin, G.OPA_IM2COL, b_mode, c_mode, G.Conv(b, h, w, cin, rs, cin),
+                      ldb=T * cin, ldc=64, conv_cout=cin)
+    return rc == 0
+
+
 def test_halo_copy_agrees_with_the_host_mirror():
+    """Halo-tile eligibility: the library's launch validation (encdiff_gemm_check) and ops.halo_fits,
+    which asks it, against this file's restatement G.halo_ok."""
     from encdiff_amd import ops as O
-    assert O.HALO_TILES == G.HALO_TILES and O.HALO_LDS_MAX == G.HALO_LDS_MAX
+    assert O.HALO_TILES == G.HALO_TILES
     n = 0
     for tile in list(G.HALO_TILES) + [4, 24]:
         for b, h, w in ((64, 2, 2), (16, 4, 4), (4, 8, 8), (2, 16, 16), (1, 32, 32), (2, 64, 64), (3, 4, 8), (2, 6, 6)):
             for cin in (8, 12, 24, 64, 128, 192, 256, 512):
                 for rs in (0, 1, 2, 3, 4, 5):
                     for split in (1, 2, 4):
-                        assert O.halo_fits(tile, b, h, w, cin, rs, split) == G.halo_ok(tile, b, h, w, cin, rs, split), \
-                            (tile, b, h, w, cin, rs, split)
-                        n += 1
-    assert n > 1000
+                        for bm in (G.OPB_ROWK, G.OPB_CONV_DGRAD):
+                            for cm in (G.OUT_BF16, G.OUT_F32_ATOMIC):
+                                want = G.halo_ok(tile, b, h, w, cin, rs, split, b_mode=bm, c_mode=cm)
+                                case = (tile, b, h, w, cin, rs, split, bm, cm)
+                                assert O.halo_fits(tile, b, h, w, cin, rs, split, b_mode=bm, c_mode=cm) == want, case
+                                if tile != 4:  # a ring tile: launches, but is no halo tile
+                                    assert lib_halo(tile, b, h, w, cin, rs, split, bm, cm) == want, case
+                                    n += 1
+                        assert O.halo_fits(tile, b, h, w, cin, rs, split) == G.halo_ok(tile, b, h, w, cin, rs, split)
+    assert n > 40000, n
+    # the LDS limit, tile by tile: the widest window the restatement lets in is accepted, 8 more
+    # source channels are refused
+    for tile in G.HALO_TILES:
+        for geom in ((2, 16, 16), (1, 32, 32)):
+            fit = [cin for cin in range(8, 4097, 8) if G.halo_ok(tile, *geom, cin, G.NONE)]
+            if fit and max(fit) < 4096:
+                break
+        assert fit and max(fit) < 4096, (tile, "no LDS boundary below cin = 4096")
+        top = max(fit)
+        assert not G.halo_ok(tile, *geom, top + 8, G.NONE)
+        assert lib_halo(tile, *geom, top, G.NONE) and O.halo_fits(tile, *geom, top, G.NONE), (tile, geom, top)
+        assert not lib_halo(tile, *geom, top + 8, G.NONE) and not O.halo_fits(tile, *geom, top + 8, G.NONE), (tile, top)
+
+
+def lib_wg3(tile, b, h, cout, cin, rs, lda, c_mode, split, ldc=None, **ptrs):
+    rc, _ = lib_check(tile, split, cout, 9 * cin, b * h * h, G.OPA_ROWM, G.OPB_IM2COL, c_mode,
+                      G.Conv(b, h, h, cin, rs, cin), lda=lda, ldc=9 * cin if ldc is None else ldc, **ptrs)
+    return rc == 0
+
+
+def lib_wgl(M, N, K, lda, ldb, c_mode, split, ldc=None, **ptrs):
+    rc, _ = lib_check(36, split, M, N, K, G.OPA_ROWM, G.OPB_ROWN, c_mode, lda=lda, ldb=ldb,
+                      ldc=N if ldc is None else ldc, **ptrs)
+    return rc == 0
 
 
 def test_wg_copies_agree_with_the_host_mirrors():
     """ops.wg3_split / ops.wgl_split return a split the kernels accept (or None where no split
-    is eligible): the copies of the device-side checks must accept exactly those."""
+    is eligible), and the library's own check of tiles 32-34 / 36 accepts exactly the explicit
+    splits the copies of the device-side checks accept."""
     from encdiff_amd import ops as O
+    n3 = nl = 0
     for tile in (32, 33, 34):
         for b in (1, 2, 4, 6, 8, 16, 32, 128):
             for h in (2, 4, 8, 16, 32):
@@ -259,6 +321,11 @@ def test_wg_copies_agree_with_the_host_mirrors():
                             assert (sp is not None) == any_ok, (tile, b, h, cout, cin, rs, ld)
                             if sp is not None:
                                 assert G.wg3_ok(tile, b, h, h, cout, cin, rs, ld, cin, G.OUT_F32_ACCUM, sp)
+                            for split in (1, 2, 3, 4, 8):
+                                want = G.wg3_ok(tile, b, h, h, cout, cin, rs, ld, cin, G.OUT_F32_ACCUM, split)
+                                assert lib_wg3(tile, b, h, cout, cin, rs, ld, G.OUT_F32_ACCUM, split) == want, \
+                                    (tile, b, h, cout, cin, rs, ld, split)
+                                n3 += 1
     for M in (64, 128, 72):
         for N in (64, 96, 128):
             for K in (128, 256, 512, 768, 1000):
@@ -266,26 +333,114 @@ def test_wg_copies_agree_with_the_host_mirrors():
                     sp = O.wgl_split(M, N, K, M + ld, N, G.OUT_F32_ACCUM)
                     if sp is not None:
                         assert G.wgl_ok(M, N, K, M + ld, N, G.OUT_F32_ACCUM, sp)
-                    else:  # the mirror also declines K % 256 != 0 and plans without two stages per wave
+                    else:  # the policy also declines K % 256 != 0 and plans without two stages per wave
                         assert (not G.wgl_ok(M, N, K, M + ld, N, G.OUT_F32_ACCUM, 1)) or K % 256 or K < 256
+                    for split in (1, 2, 3, 4, 6):
+                        want = G.wgl_ok(M, N, K, M + ld, N, G.OUT_F32_ACCUM, split)
+                        assert lib_wgl(M, N, K, M + ld, N, G.OUT_F32_ACCUM, split) == want, (M, N, K, ld, split)
+                        nl += 1
+    assert n3 > 10000 and nl > 400
     assert not G.wgl_ok(64, 64, 256, 64, 64, G.OUT_BF16, 1) and not G.wgl_ok(64, 64, 768, 64, 64, G.OUT_F32, 4)
     assert G.wgl_ok(64, 64, 768, 64, 64, G.OUT_F32, 3)
+    # float4 epilogue stores: with one split C itself (ldc % 4, 16-byte aligned), else the slabs;
+    # A and B always 16-byte aligned
+    for split in (1, 2):
+        for ldc in (9 * 16, 9 * 16 + 2):
+            for bad in (None, "pa", "pb", "pc", "ws"):
+                p = dict(pa=PTR, pb=2 * PTR, pc=3 * PTR, ws=WS)
+                if bad:
+                    p[bad] += 8
+                seen = (p["pa"], p["pb"], p["pc"] if split == 1 else p["ws"])
+                want = G.wg3_ok(32, 8, 16, 16, 32, 16, 0, 32, 16, G.OUT_F32_ACCUM, split, ldc=ldc, ptrs=seen)
+                assert want == (not (bad in ("pa", "pb", "pc" if split == 1 else "ws") or (split == 1 and ldc % 4)))
+                assert lib_wg3(32, 8, 16, 32, 16, 0, 32, G.OUT_F32_ACCUM, split, ldc=ldc, **p) == want, (split, ldc, bad)
+                want = G.wgl_ok(64, 64, 512, 64, 64, G.OUT_F32_ACCUM, split, ldc=ldc, ptrs=seen)
+                assert lib_wgl(64, 64, 512, 64, 64, G.OUT_F32_ACCUM, split, ldc=ldc, **p) == want, (split, ldc, bad)
+
+
+REFUSALS = [  # (refused, M, N, K, a_mode, b_mode, c_mode, conv, bias_grad / gn_stats)
+    (False, 512, 16, 32, G.OPA_IM2COL, G.OPB_CONV_DGRAD, G.OUT_BF16, G.Conv(32, 4, 4, 8, G.K4S2_TP, 8), {}),
+    (True, 512, 16, 32, G.OPA_IM2COL, G.OPB_CONV_DGRAD, G.OUT_F32_ATOMIC, G.Conv(32, 4, 4, 8, G.K4S2_TP, 8), {}),
+    (True, 512, 16, 32, G.OPA_IM2COL, G.OPB_ROWK, G.OUT_BF16, G.Conv(32, 4, 4, 8, G.K4S2_TP, 8), {}),
+    (True, 512, 16, 128, G.OPA_IM2COL, G.OPB_CONV_DGRAD, G.OUT_BF16, G.Conv(32, 4, 4, 8, G.K4S2_TP, 8), {}),  # K != 4 cin
+    (True, 256, 16, 32, G.OPA_IM2COL, G.OPB_CONV_DGRAD, G.OUT_BF16, G.Conv(16, 4, 4, 8, G.K4S2_TP, 8), {}),
+    (True, 64, 16, 72, G.OPA_IM2COL, G.OPB_ROWK, G.OUT_BF16, G.Conv(1, 8, 8, 8, G.DOWN2, 8), {}),
+    (True, 64, 16, 36, G.OPA_ROWK, G.OPB_ROWK, G.OUT_BF16, None, {}),                                          # K % 8
+    (True, 60, 16, 64, G.OPA_ROWM, G.OPB_ROWN, G.OUT_F32, None, {}),                                           # M % 8
+    (True, 64, 20, 64, G.OPA_ROWK, G.OPB_ROWN, G.OUT_BF16, None, {}),                                          # N % 8
+    (False, 64, 20, 64, G.OPA_ROWK, G.OPB_ROWK, G.OUT_BF16, None, {}),
+    (True, 64, 16, 64, G.OPA_ROWK, G.OPB_ROWK, G.OUT_BF16, None, dict(bias_grad=True)),
+    (True, 72, 16, 64, G.OPA_ROWK, G.OPB_ROWK, G.OUT_BF16, None, dict(gn_stats=True)),
+]
 
 
 def test_refusal_copy_by_hand():
-    cv = G.Conv(32, 4, 4, 8, G.K4S2_TP, 8)
-    assert not G.gemm_refused(512, 16, 32, G.OPA_IM2COL, G.OPB_CONV_DGRAD, G.OUT_BF16, cv)
-    assert G.gemm_refused(512, 16, 32, G.OPA_IM2COL, G.OPB_CONV_DGRAD, G.OUT_F32_ATOMIC, cv)
-    assert G.gemm_refused(512, 16, 32, G.OPA_IM2COL, G.OPB_ROWK, G.OUT_BF16, cv)
-    assert G.gemm_refused(512, 16, 128, G.OPA_IM2COL, G.OPB_CONV_DGRAD, G.OUT_BF16, cv)            # K != 4 cin
-    assert G.gemm_refused(256, 16, 32, G.OPA_IM2COL, G.OPB_CONV_DGRAD, G.OUT_BF16, G.Conv(16, 4, 4, 8, G.K4S2_TP, 8))
-    assert G.gemm_refused(64, 16, 72, G.OPA_IM2COL, G.OPB_ROWK, G.OUT_BF16, G.Conv(1, 8, 8, 8, G.DOWN2, 8))
-    assert G.gemm_refused(64, 16, 36, G.OPA_ROWK, G.OPB_ROWK, G.OUT_BF16)                            # K % 8
-    assert G.gemm_refused(60, 16, 64, G.OPA_ROWM, G.OPB_ROWN, G.OUT_F32)                             # M % 8
-    assert G.gemm_refused(64, 20, 64, G.OPA_ROWK, G.OPB_ROWN, G.OUT_BF16)                            # N % 8
-    assert not G.gemm_refused(64, 20, 64, G.OPA_ROWK, G.OPB_ROWK, G.OUT_BF16)
-    assert G.gemm_refused(64, 16, 64, G.OPA_ROWK, G.OPB_ROWK, G.OUT_BF16, bias_grad=True)
-    assert G.gemm_refused(72, 16, 64, G.OPA_ROWK, G.OPB_ROWK, G.OUT_BF16, gn_stats=True)
+    """The tile-independent refusals, by hand; the library's check (tile 4) agrees with the copy."""
+    for want, M, N, K, am, bm, cm, cv, kw in REFUSALS:
+        assert G.gemm_refused(M, N, K, am, bm, cm, cv, **kw) == want
+        ptrs = dict(bias_grad=PTR) if kw.get("bias_grad") else (dict(gn_stats=PTR, ld_gn_stats=N) if kw else {})
+        cout = K // G.taps(cv.resample)[0] if bm == G.OPB_CONV_DGRAD else 0
+        rc, tile = lib_check(4, 1, M, N, K, am, bm, cm, cv, lda=K, ldb=max(K, N), ldc=N, conv_cout=cout, **ptrs)
+        assert (rc != 0) == want and (want or tile == 4), (M, N, K, am, bm, cm, rc, tile)
+
+
+def test_tile_shapes_come_from_the_library():
+    """encdiff_gemm_tile_shape: the ring and halo tiles' (BM, BN, KB, ring depth); every other id --
+    auto, the gaps, the WG3 / WGL kernel ids -- is no tile shape."""
+    import ctypes as C
+    import encdiff_amd._lib as L
+    from encdiff_amd import ops as O
+
+    def shape(tile):
+        v = [C.c_int(-1) for _ in range(4)]
+        rc = L.lib.encdiff_gemm_tile_shape(tile, *(C.byref(x) for x in v))
+        return rc, tuple(x.value for x in v)
+    for tile in list(G.RING_TILES) + list(G.HALO_TILES):
+        assert shape(tile) == (0, G.tile_shape(tile)), tile
+    for tile in [0] + list(range(11, 16)) + [24] + list(range(32, 37)) + [-1, 1 << 20]:
+        assert shape(tile) == (-3, (-1,) * 4), tile   # ENCDIFF_ERR_UNSUPPORTED, nothing written
+    assert L.lib.encdiff_gemm_tile_shape(19, None, None, None, None) == 0
+    assert O.HALO_TILES == G.HALO_TILES
+    assert lib_check(0, 1, 64, 64, 64, 0, 0, 0, lda=64, ldb=64, ldc=64) == (0, 4)        # the default the launch picks
+    assert lib_check(0, 1, 4096, 4096, 64, 0, 0, 0, lda=64, ldb=64, ldc=4096) == (0, 1)
+    assert L.lib.encdiff_gemm_check(None, None) == -1
+
+
+def test_measured_table_is_valid_where_it_was_measured():
+    """Every entry of the measured tile table, at its own geometry (w = h; the batch from M for an
+    im2col A, from K for an im2col B), is a plan the library accepts: keys carry (M, N, K, h), so at
+    another batch, stride or alignment ops.gemm_args asks again (and falls back to the generic plan)."""
+    import json
+    import os
+    import encdiff_amd
+    table = json.load(open(os.path.join(os.path.dirname(encdiff_amd.__file__), "gemm_tiles.json")))
+    n = geglu = 0
+    for key, v in table.items():
+        if not isinstance(v, list):   # "wg3,..." keys: a measured split alone
+            continue
+        parts = key.split(",")
+        am, bm, cm, M, N, K = map(int, parts[:6])
+        rs = h = 0
+        for p in parts[6:]:
+            rs, h = (int(p[1:]), h) if p[0] == "r" else (rs, int(p[1:]))
+        tile, split = int(v[0]), int(v[1])
+        conv, cout, T = None, 0, G.taps(rs)[0]
+        if am == G.OPA_IM2COL or bm == G.OPB_IM2COL:
+            if not h:
+                continue
+            batch, cin = (M // (h * h), K // T) if am == G.OPA_IM2COL else (K // (h * h), N // T)
+            conv = G.Conv(batch, h, h, cin, rs, cin)
+        ldb = {G.OPB_ROWK: K, G.OPB_ROWN: N, G.OPB_IM2COL: 0}.get(bm)
+        if bm == G.OPB_CONV_DGRAD:  # packed weights [cout][taps * N]
+            cout, ldb = K // T, (16 if rs in (G.K4S2_T, G.K4S2_TP) else 9) * N
+        kw = {}
+        if cm in (5, 6):  # the GEGLU epilogues: y output / f input
+            kw, geglu = dict(aux=PTR, ld_aux=N), geglu + 1
+        rc, t = lib_check(tile, split, M, N, K, am, bm, cm, conv, lda=M if am == G.OPA_ROWM else K, ldb=ldb, ldc=N,
+                          conv_cout=cout, **kw)
+        assert (rc, t) == (0, tile), (key, v[:2], rc)
+        n += 1
+    assert n > 200 and geglu > 0
 
 
 def test_pair_route_by_hand():

@@ -291,7 +291,8 @@ def run(O, M, N, K, a, b, *, tile, split=1, fold=False, a_mode=0, b_mode=0, c_mo
 
 
 def refused(O, M, N, K, a, b, *, tile, split=1, c_mode=G.OUT_F32, **kw):
-    """The library must refuse the launch (HipError) and write nothing."""
+    """The library must refuse the launch (HipError) and write nothing; encdiff_gemm_check, the
+    host-only query of the same validation, must refuse the same arguments."""
     out_dt = BF16 if c_mode == G.OUT_BF16 else F32
     out = Guard(M, N, out_dt, init=torch.zeros(M, N, dtype=out_dt, device=E.dev))
     conv = kw.pop("conv", None)
@@ -300,6 +301,10 @@ def refused(O, M, N, K, a, b, *, tile, split=1, c_mode=G.OUT_F32, **kw):
         src = a if kw.get("a_mode", 0) == G.OPA_IM2COL else b
         cg = O.L.ConvGeom(batch=conv[0], h=conv[1], w=conv[2], cin=conv[3], resample=conv[4], ld_src=src.stride(0))
     O.flush()
+    args = O.gemm_args(M, N, K, a, a.stride(0), b, b.stride(0), out.view, N, c_mode=c_mode, conv=cg, split_k=split,
+                       tile=tile, **kw)
+    assert (args.tile, args.split_k) == (tile, split)
+    assert O.L.lib.encdiff_gemm_check(args, None) != 0
     with pytest.raises(O.L.HipError):
         O.gemm(M, N, K, a, a.stride(0), b, b.stride(0), out.view, N, c_mode=c_mode, conv=cg, split_k=split,
                tile=tile, **kw)
