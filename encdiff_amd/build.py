@@ -37,7 +37,7 @@ def _headers():
 # per-file extra flags: the attention kernels' softmax max trees need no NaN canonicalisation;
 # the norm kernels contract a*b+c only within one source expression (-ffp-contract=on): their
 # template instantiations (GroupNorm backward with / without slab input, the split-K combine
-# restated from gemm.hip) must round identically, and "fast" fuses across statements
+# restated from gemm_finalize.h) must round identically, and "fast" fuses across statements
 # differently per instantiation (test_unet_gn_fin_bitwise)
 FILE_FLAGS = {"attn_mfma.hip": ["-fno-honor-nans", "-mno-amdgpu-ieee"], "norm.hip": ["-ffp-contract=on"]}
 

@@ -167,7 +167,7 @@ ED_DEV uint4 gn_row(const GnSlice& L, const uint4* tile, const bf16_t* g, long l
 }
 
 // x as the deferred split-K finalize of its producer GEMM (EncdiffGroupNormArgs.x_from): fp32
-// slabs [split][M][C] behind ws, C = alpha * sum_z slab[z] (+ bias)(+ resid) -- gemm.hip's
+// slabs [split][M][C] behind ws, C = alpha * sum_z slab[z] (+ bias)(+ resid) -- gemm_finalize.h's
 // gemm_finalize, same summation order (one ordered sum up to 8 slabs, else four z-groups added
 // ((0 + 1) + 2) + 3), same rounding -- so x is bitwise what the finalize pass would have written.
 struct GnSlabs {
@@ -195,7 +195,7 @@ ED_DEV void gn_slab_batch(const float* w, long stride, int z0, int split, float 
 }
 
 ED_DEV uint4 gn_slab_row(const GnSlabs& sl, long row, int c, int cb) {
-  // alpha / bias through splitk_scale: gemm.hip's gemm_finalize does this combine too, bitwise alike
+  // alpha / bias through splitk_scale: gemm_finalize.h's gemm_finalize does this combine too, bitwise alike
   const float* w = sl.ws + row * c + cb;
   float a[8], v[8][8];
   if (sl.split <= 8) {

@@ -333,7 +333,7 @@ __global__ __launch_bounds__(64 * NWV) void st_tail_kernel(const EncdiffStTailAr
   }
   if constexpr (R == 64 || R == 32) {
     if (p.gn_stats) {
-      // the next GroupNorm's statistics of this 64-row segment (gemm.hip's gn_stats layout): per
+      // the next GroupNorm's statistics of this 64-row segment (gemm_tile.h's gn_stats layout): per
       // column sum and sum of squares of the stored bf16 values, TPC row groups added in order;
       // a 32-row tile adds its half of the segment into the zeroed slot (gn_stats_add: with two
       // addends 0 + a + b has the same bits in either order)

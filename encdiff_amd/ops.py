@@ -120,7 +120,7 @@ FORCE_TILE = 0  # tests: override the planned tile of every GEMM that does not p
 
 
 # Which (tile, split_k) plans are legal for a GEMM is decided in ONE place, the library's launch
-# validation (gemm.hip prepare()), asked through encdiff_gemm_check -- host arithmetic, no HIP call.
+# validation (gemm_plan.h prepare()), asked through encdiff_gemm_check -- host arithmetic, no HIP call.
 # This module owns the policy only: table lookup, split heuristics, workspace capacity.
 WG3_TILES = (32, 33, 34)  # ids of the 3x3 conv weight-gradient kernel (WG3): kernels, not tile shapes
 WGL_TILE = 36             # id of the linear weight-gradient kernel (WGL)
@@ -128,7 +128,7 @@ _WS_STANDIN = 1 << 12     # workspace address of a plan being checked: aligned a
 
 
 def _tile_dims():
-    """tile id -> (BM, BN, KB, ring depth) of every ring / halo tile, as gemm.hip states them."""
+    """tile id -> (BM, BN, KB, ring depth) of every ring / halo tile, as gemm_plan.h states them."""
     dims = {}
     for t in range(1, 32):
         v = [C.c_int() for _ in range(4)]
@@ -138,7 +138,7 @@ def _tile_dims():
 
 
 _TILE_DIMS = _tile_dims()
-# halo tiles (gemm.hip tiles 16-23): BM x BN, window staged once per workgroup
+# halo tiles (gemm_plan.h tiles 16-23): BM x BN, window staged once per workgroup
 HALO_TILES = {t: d[:2] for t, d in _TILE_DIMS.items() if t >= 16}
 
 
@@ -229,7 +229,7 @@ WG3_SPLIT = 0  # experiments: force the WG3 split
 
 
 def wg3_split(batch, h, w, cout, cin, resample, lda, ld_src, c_mode, tile=None):
-    """Pixel chunks (split) of a 3x3 conv weight gradient on gemm.hip's WG3 kernel, or None when
+    """Pixel chunks (split) of a 3x3 conv weight gradient on gemm_wg3.h's WG3 kernel, or None when
     the library does not take the problem on that kernel (encdiff_gemm_check decides; operands
     16-byte aligned).  A workgroup owns 32 couts x 16 cins x 9 taps of one chunk of whole images;
     its 4 (tile 32) or 8 (tile 33) waves split the chunk's 32-pixel stages: the largest
@@ -260,7 +260,7 @@ WGL = int(os.environ.get("ENCDIFF_WGL", "1"))
 
 
 def wgl_split(M, N, K, lda, ldb, c_mode):
-    """Token chunks (split) of a linear weight gradient dW[M][N] += dY^T x on gemm.hip's WGL kernel
+    """Token chunks (split) of a linear weight gradient dW[M][N] += dY^T x on gemm_wgl.h's WGL kernel
     (tile 36), or None when the library does not take the problem on that kernel (encdiff_gemm_check
     decides; operands 16-byte aligned) or K % 256: workgroups own 64 x 64 output parts, their 4 waves
     a quarter of a chunk each in 32-token stages; the largest power-of-two split the library accepts

@@ -1,4 +1,4 @@
-"""The XCD-aware tile order (gemm.hip xcd_remap, ENCDIFF_GEMM_XCD) only changes WHICH workgroup
+"""The XCD-aware tile order (gemm_tile.h xcd_remap, ENCDIFF_GEMM_XCD) only changes WHICH workgroup
 computes a tile, never the arithmetic of a tile: one eager training step (B=32, every GEMM form --
 forward convs / linears, paired input / weight gradients, WG3 / WGL grids, split-K slabs and
 their finalizes) must give bitwise the same gradient arena and updated weights with the order off

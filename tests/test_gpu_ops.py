@@ -418,7 +418,7 @@ def test_conv3x3(O, B, H, cin, cout, mode):
                                                 (16, 4, 512, 256, 2), (8, 8, 64, 32, 0)])
 @pytest.mark.parametrize("tile", [32, 33, 34])
 def test_conv3x3_wgrad_wg3(O, B, H, cin, cout, mode, tile, monkeypatch):
-    """The 3x3 weight-gradient kernel (gemm.hip WG3, tile 32) vs a torch fp32 reference and vs the
+    """The 3x3 weight-gradient kernel (gemm_wg3.h WG3, tile 32) vs a torch fp32 reference and vs the
     split-K GEMM form: dW (channels-last, accumulated onto a nonzero dW) and the bias gradient;
     then two paired backward launches in a row (the first's finalize deferred into the second).
     The heuristic WG3 plan is what is tested here (no tuned-table override, ops.TABLE_WG)."""
@@ -473,7 +473,7 @@ def test_conv3x3_wgrad_wg3(O, B, H, cin, cout, mode, tile, monkeypatch):
 @pytest.mark.parametrize("T,cout,cin", [(32768, 64, 64), (8192, 128, 128), (2048, 256, 256), (32768, 512, 64),
                                          (8192, 1024, 128), (2048, 2048, 256), (256, 64, 128), (2048, 192, 64)])
 def test_linear_wgrad_wgl(O, T, cout, cin, monkeypatch):
-    """The linear weight-gradient kernel (gemm.hip WGL, tile 36) vs a torch fp32 reference and vs
+    """The linear weight-gradient kernel (gemm_wgl.h WGL, tile 36) vs a torch fp32 reference and vs
     the split-K GEMM form (dW accumulated onto a nonzero dW, bias gradient), then two paired
     backward launches in a row (input gradient in the same grid, the first finalize deferred)."""
     monkeypatch.setattr(O, "TABLE_WG", 0)  # the heuristic WGL plan (no tuned-table override)

@@ -111,7 +111,7 @@ def test_dp_split_layout(params):
 
 def test_wg3_split_matches_kernel_rule():
     """ops.wg3_split (host plan of the 3x3 weight-gradient kernel WG3) only returns splits that
-    gemm.hip wg3_check accepts: whole-image chunks (images per chunk a multiple of the images per
+    gemm_plan.h wg3_check accepts: whole-image chunks (images per chunk a multiple of the images per
     32-pixel stage) whose stage count divides over the workgroup's waves; odd batches fall back."""
     from encdiff_amd import ops, _lib as L
     for B in (1, 2, 3, 4, 6, 8, 16, 32, 64, 128, 512):

@@ -1,4 +1,4 @@
-"""Time the 3x3 conv weight gradients of one B=128 training step: the WG3 kernel (gemm.hip
+"""Time the 3x3 conv weight gradients of one B=128 training step: the WG3 kernel (gemm_wg3.h
 tile 32) against the split-K GEMM form (the measured table's tile / split), each launch with
 its finalize, and the paired backward (weight + input gradient) both ways.
 

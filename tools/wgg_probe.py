@@ -21,7 +21,7 @@ sys.path.insert(0, REPO)
 
 KINDS = {0: "WG3 16", 1: "WG3 16 up", 2: "WG3 8", 3: "WG3 8 up", 4: "WG3 4", 5: "WG3 4 up", 6: "WGL",
          7: "gen lin", 8: "gen conv"}
-PROB_BYTES = 576  # sizeof(WgProb) in gemm.hip
+PROB_BYTES = 576  # sizeof(WgProb) in gemm_group.h
 
 
 def main():

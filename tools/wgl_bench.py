@@ -1,5 +1,5 @@
 """Linear backward pairs of one B=128 training step: weight gradient on the split-K GEMM vs the WGL
-kernel (gemm.hip tile 36), each paired with its input gradient (graph-timed, finalize flushed).
+kernel (gemm_wgl.h tile 36), each paired with its input gradient (graph-timed, finalize flushed).
 
     python tools/wgl_bench.py
 """
