@@ -217,6 +217,7 @@ extern "C" int encdiff_encoder_warp_fwd(const float* u, long ldu, int batch, int
                                         long unit_stride, int context_dim, float* out, long ldo, void* stream) {
   if (!u || !params || !out || batch <= 0 || units <= 0) return ENCDIFF_ERR_ARG;
   if (context_dim <= 0 || context_dim > 16) return ENCDIFF_ERR_UNSUPPORTED;
+  if (ldu < units || ldo < (long)units * context_dim) return ENCDIFF_ERR_ARG;  // rows narrower than the data
   if (unit_stride < 2 * H1 + H2 * H1 + H2 + context_dim * H2 + context_dim) return ENCDIFF_ERR_SHAPE;
   static const hipError_t attr = hipFuncSetAttribute((const void*)warp_fwd_kernel,
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -236,6 +237,7 @@ extern "C" int encdiff_encoder_warp_bwd(const float* u, long ldu, int batch, int
                                         long lddu, float* grads, float* partials, void* stream) {
   if (!u || !params || !dout || !du || !grads || !partials || batch <= 0 || units <= 0) return ENCDIFF_ERR_ARG;
   if (context_dim <= 0 || context_dim > 16) return ENCDIFF_ERR_UNSUPPORTED;
+  if (ldu < units || lddu < units || lddo < (long)units * context_dim) return ENCDIFF_ERR_ARG;
   if (unit_stride < 2 * H1 + H2 * H1 + H2 + context_dim * H2 + context_dim) return ENCDIFF_ERR_SHAPE;
   static const hipError_t attr = hipFuncSetAttribute((const void*)warp_bwd_kernel,
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -401,7 +403,8 @@ extern "C" int encdiff_encoder_head_fwd(const float* r, long ldr, int batch, int
 extern "C" int encdiff_encoder_head_bwd(const float* r, long ldr, int batch, int d, const float* W, int units,
                                         const float* du, long lddu, void* dr, long lddr, float* dW, float* db,
                                         void* stream) {
-  if (!r || !W || !du || !dr || !dW || !db || batch <= 0 || d <= 0 || units <= 0 || units > 64 || lddr < d)
+  if (!r || !W || !du || !dr || !dW || !db || batch <= 0 || d <= 0 || units <= 0 || units > 64 || lddr < d ||
+      ldr < d || lddu < units)
     return ENCDIFF_ERR_ARG;
   const int um = units <= 20 ? 20 : (units <= 40 ? 40 : 64);
   size_t lds = (size_t)(batch < HEAD_CB ? batch : HEAD_CB) * um * sizeof(float);

@@ -556,7 +556,9 @@ int encdiff_gather_images_u8(const void* pool, long long n_images, int h, int w,
  * [W1 64][b1 64][W2 128x64][b2 128][W3 context_dim x 128][b3 context_dim] (the layout
  * of the parameter arena).  The backward ADDS the weight gradients into `grads` (same
  * layout) and writes du: one workgroup per (unit, 8-row batch chunk), chunk partials in
- * `partials`, folded in a fixed order by a second launch (deterministic). context_dim <= 16. */
+ * `partials`, folded in a fixed order by a second launch (deterministic). context_dim <= 16.
+ * Leading dimensions narrower than the data (ldu / lddu < units, ldo / lddo < units*context_dim)
+ * are refused with ENCDIFF_ERR_ARG. */
 int encdiff_encoder_warp_fwd(const float* u, long ldu, int batch, int units, const float* params,
                              long unit_stride, int context_dim, float* out, long ldo, void* stream);
 int encdiff_encoder_warp_bwd(const float* u, long ldu, int batch, int units, const float* params,
@@ -567,7 +569,8 @@ int encdiff_encoder_warp_bwd(const float* u, long ldu, int batch, int units, con
  * (element (b, c, p) at r[(b*16 + p)*ldr + c], column k = c*16 + p of W [units][d*16], the
  * reference layout).  fp32.  fwd: u [batch][ldu] = x W^T + bias.  bwd (one launch): dr (bf16
  * NHWC rows, the trunk's output gradient) = du W, dW += du^T x, db += sum_b du (batch order,
- * deterministic).  Replaces the flatten copy, the Linear GEMMs and their gradient adds. */
+ * deterministic).  Replaces the flatten copy, the Linear GEMMs and their gradient adds.
+ * units <= 64 (bwd); ldr / lddr < d and ldu / lddu < units are refused with ENCDIFF_ERR_ARG. */
 int encdiff_encoder_head_fwd(const float* r, long ldr, int batch, int d, const float* W, const float* bias,
                              int units, float* u, long ldu, void* stream);
 int encdiff_encoder_head_bwd(const float* r, long ldr, int batch, int d, const float* W, int units,
