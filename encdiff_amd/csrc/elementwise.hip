@@ -722,6 +722,8 @@ int sconv_wgs() {
   return v;
 }
 
+bool vec16(const void* q) { return ((uintptr_t)q & 15) == 0; }
+
 int grid_for(long n, int per_thread = 1) {
   long g = (n / per_thread + 255) / 256;
   if (g > 4096) g = 4096;
@@ -747,9 +749,11 @@ extern "C" int encdiff_small_conv_fwd(const EncdiffSmallConvArgs* a, void* strea
   const long pix = (long)a->batch * a->h * a->w;
   if (a->x_f32 && !a->y_f32) {  // input conv
     if (a->cin > 4 || a->cout > 64 || a->cout % 8 || a->ldy % 8) return ENCDIFF_ERR_SHAPE;
+    if (!vec16(a->y)) return ENCDIFF_ERR_ARG;  // 16-byte stores of 8 bf16 outputs
     hipLaunchKernelGGL(small_conv_in_fwd, dim3(grid_for(pix)), dim3(256), 0, s, *a);
   } else if (!a->x_f32 && a->y_f32) {  // output conv
     if (a->cout > 3 || a->cin > 512 || a->cin % 8) return ENCDIFF_ERR_SHAPE;
+    if (!vec16(a->x) || a->ldx % 8) return ENCDIFF_ERR_ARG;  // 16-byte loads of 8 bf16 channels
     const int v = a->cin / 8;
     if ((v & (v - 1)) == 0 && pix * v < (1L << 31)) {  // 32-bit indices in the lane kernel  // power-of-two chunk count (<= 64): lane groups within a wave
       int vshift = 0;
@@ -774,6 +778,7 @@ extern "C" int encdiff_small_conv_bwd(const EncdiffSmallConvArgs* a, void* strea
   if (a->dx) {
     if (!a->dy_f32 || a->cout > 3 || a->cin % 8) return ENCDIFF_ERR_UNSUPPORTED;
     if (a->cin > 512) return ENCDIFF_ERR_SHAPE;  // LDS weight copy holds 3 x 9 x 512
+    if (!vec16(a->dx) || a->lddx % 8) return ENCDIFF_ERR_ARG;  // 16-byte stores of 8 bf16 channels
     if ((long)a->batch * HW * (a->cin / 8) >= (1L << 31)) return ENCDIFF_ERR_SHAPE;  // 32-bit indices
     hipLaunchKernelGGL(small_conv_out_dgrad, dim3(std::min(grid_for((long)a->batch * HW * (a->cin / 8)), sconv_wgs())),
                        dim3(256), (size_t)3 * 9 * a->cin * sizeof(float), s, *a);

@@ -403,6 +403,10 @@ int encdiff_elementwise(const EncdiffEwArgs* args, void* stream);
  * UNet input conv 3->64 (openaimodel_enc.py:521) and output conv 64->3
  * (openaimodel_enc.py:687): channel counts not multiples of 8.  NHWC bf16
  * activations, fp32 weights in the reference layout [co][ci][3][3].
+ * The bf16 rows are read and written as 16-byte vectors: the bf16 x of the
+ * output conv, its dx and the bf16 y of the input conv must be 16-byte aligned
+ * with ldx / lddx / ldy multiples of 8 elements (ENCDIFF_ERR_ARG otherwise;
+ * ldy % 8 of the input conv is reported as ENCDIFF_ERR_SHAPE).
  */
 typedef struct EncdiffSmallConvArgs {
   int batch, h, w, cin, cout;

@@ -92,18 +92,18 @@ def test_torch_library_ops_registered():
                                    torch.zeros(1000), torch.zeros(1000))
 
 
+class StWg(C.Structure):  # st_bwd.hip / stwg.h StWg (plan blob, after a 64-byte header)
+    _fields_ = [("dy", C.c_void_p), ("x", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p),
+                ("slab", C.c_void_p), ("ld_dy", C.c_long), ("ld_x", C.c_long), ("ld_dw", C.c_long)] + \
+               [(n, C.c_int) for n in ("M", "N", "K", "kc", "kb", "mb", "nb", "item0", "fold0", "kind", "bm", "bn")]
+
+
 def test_st_wgrad_plan_layout():
     """Host logic of encdiff_st_wgrad_plan (no GPU): for a c = 64 / 128 transformer block's eight
     weight gradients at the training batch the plan covers every token in chunks, gives each problem
     a slab region of its own inside the workspace (no overlap), numbers work items and fold blocks
     contiguously, and doubles the chunk length until the slabs fit a small workspace."""
     import encdiff_amd._lib as L
-
-    class StWg(C.Structure):  # st_bwd.hip / stwg.h StWg (plan blob, after a 64-byte header)
-        _fields_ = [("dy", C.c_void_p), ("x", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p),
-                    ("slab", C.c_void_p), ("ld_dy", C.c_long), ("ld_x", C.c_long), ("ld_dw", C.c_long)] + \
-                   [(n, C.c_int) for n in ("M", "N", "K", "kc", "kb", "mb", "nb", "item0", "fold0", "kind", "bm",
-                                           "bn")]
     base = 1 << 32
     for c, K in ((64, 32768), (128, 8192)):
         shapes = [(c, c, True), (3 * c, c, False), (c, c, True), (c, c, False), (c, c, True), (8 * c, c, True),

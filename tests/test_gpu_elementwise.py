@@ -35,6 +35,8 @@ Kernel branch -> test
   grad_fold_kernel: padding channels, db / gb, refusals ................. test_grad_fold
   gather_u8_kernel: byte-wise staging, 16-byte staging, id clamp ........ test_gather_images_u8_small
   bn_stats / bn_apply: x_f32, y_split, encdiff_batchnorm_apply .......... test_batchnorm_forms
+  small_conv_in_fwd / out_fwd / out_fwd_lanes / out_dgrad / wgrad ....... tests/test_gpu_small_conv.py
+  step_prologue_kernel: Philox stream, t, noise tails, zero jobs ........ tests/test_gpu_step_prologue.py
 """
 import ctypes
 import math

@@ -5,7 +5,12 @@ SpatialTransformer) on the same bf16 operands: every gradient the kernels write 
 d_q2, d_t1, d_o1; d_t0, d_gn), the concept tokens' dK / dV (one tile per image and several: the
 ticket combine) and the LayerNorm affine gradients (the partial rows summed), at c = 64 / 128 and
 the row tiles the UNet's levels use (an image over several tiles: per-tile slabs folded in tile order
-by the head kernel's grid)."""
+by the head kernel's grid).
+
+The grouped weight gradients (st_wgrad_kernel, the chunk fold alone and riding in the GroupNorm
+backward) are held here to rel-L2 at the training shapes; their per-element and exact tests -- every
+block kind, short last chunks, the fold's group wrap, mixed K, strided operands, a small
+workspace -- are in tests/test_gpu_st_wgrad.py."""
 import pytest
 import torch
 import torch.nn.functional as Fn
