@@ -206,6 +206,15 @@ class ReconArgs(C.Structure):
                 ("window", vp), ("partial", vp), ("ssim", vp), ("mse", vp)]
 
 
+class GbtArgs(C.Structure):
+    _fields_ = [("n_train", C.c_int), ("n_test", C.c_int), ("dims", C.c_int), ("classes", C.c_int),
+                ("n_estimators", C.c_int), ("pad_", C.c_int), ("learning_rate", C.c_double),
+                ("tie_seed", C.c_ulonglong), ("x_train", vp), ("x_sorted", vp), ("order", vp), ("y_train", vp),
+                ("x_test", vp), ("y_test", vp), ("init_raw", vp), ("workspace", vp), ("raw_train", vp),
+                ("raw_test", vp), ("pred_train", vp), ("pred_test", vp), ("correct", vp), ("importance", vp),
+                ("trees_used", vp), ("dbg_feature", vp), ("dbg_threshold", vp), ("dbg_count", vp), ("dbg_value", vp)]
+
+
 _PROTOS = {
     "encdiff_gemm":[C.POINTER(GemmArgs), vp],
     "encdiff_gemm_pair": [C.POINTER(GemmArgs), C.POINTER(GemmArgs), vp],
@@ -283,6 +292,9 @@ _PROTOS = {
     "encdiff_tad_auroc": [vp, vp, vp, vp, C.c_longlong, C.c_int, C.c_int, vp, vp],
     "encdiff_ssim_mse": [C.POINTER(ReconArgs), vp],
     "encdiff_ssim_mse_workspace": [C.POINTER(ReconArgs), C.POINTER(C.c_longlong)],
+    "encdiff_gbt_gather": [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp],
+    "encdiff_gbt_workspace": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong)],
+    "encdiff_gbt_fit": [C.POINTER(GbtArgs), vp],
     "encdiff_version": [],
 }
 

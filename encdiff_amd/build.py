@@ -38,8 +38,10 @@ def _headers():
 # the norm kernels contract a*b+c only within one source expression (-ffp-contract=on): their
 # template instantiations (GroupNorm backward with / without slab input, the split-K combine
 # restated from gemm_finalize.h) must round identically, and "fast" fuses across statements
-# differently per instantiation (test_unet_gn_fin_bitwise)
-FILE_FLAGS = {"attn_mfma.hip": ["-fno-honor-nans", "-mno-amdgpu-ieee"], "norm.hip": ["-ffp-contract=on"]}
+# differently per instantiation (test_unet_gn_fin_bitwise); the boosted trees of DCI round every
+# product and sum on its own, as their numpy restatement does (tests/gbt_restate.py)
+FILE_FLAGS = {"attn_mfma.hip": ["-fno-honor-nans", "-mno-amdgpu-ieee"], "norm.hip": ["-ffp-contract=on"],
+              "gbt.hip": ["-ffp-contract=off"]}
 
 
 def _compile(src: str, obj: str, verbose: bool):

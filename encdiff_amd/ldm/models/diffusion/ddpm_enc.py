@@ -968,12 +968,14 @@ class LatentDiffusion(DDPM):
         return codes, toks
 
     @torch.no_grad()
-    def validation_metrics(self, codes=None, pool=None, seed=0):
+    def validation_metrics(self, codes=None, pool=None, seed=0, dci=False):
         """The FactorVAE score and MIG of eval_func (main_val.py:74-94) on the device, under its
         keys: {"factor_VAE": {train_accuracy, eval_accuracy, num_active_dims}, "MIG":
         {discrete_mig}}.  codes: (N, latent_unit) scalar codes in dataset order (device tensor or
         numpy), or pool: the validation image pool, encoded with encode_dataset.  The factor grid is
-        FactorGrid.named(self.eval_name).  beta-VAE and DCI (sklearn classifiers) are not computed."""
+        FactorGrid.named(self.eval_name).  dci=True adds "dci": {informativeness_train,
+        informativeness_test, disentanglement, completeness} (metrics.dci_score: boosted trees fitted
+        on the device, 100 stages per factor).  beta-VAE is not computed."""
         from encdiff_amd import metrics
         if (codes is None) == (pool is None):
             raise ValueError("validation_metrics takes either codes or pool")
@@ -983,8 +985,12 @@ class LatentDiffusion(DDPM):
             if n != grid.size:
                 raise ValueError(f"{n} images but the {self.eval_name} factor grid has {grid.size} observations")
             codes = self.encode_dataset(pool)[0]
-        return {"factor_VAE": metrics.factor_vae_score(codes, grid, seed=seed),
-                "MIG": metrics.mig_score(codes, grid, seed=seed)}
+        out = {"factor_VAE": metrics.factor_vae_score(codes, grid, seed=seed),
+               "MIG": metrics.mig_score(codes, grid, seed=seed)}
+        if dci:
+            res = metrics.dci_score(codes, grid, seed=seed)
+            out["dci"] = {k: res[k] for k in metrics.DCI_KEYS}
+        return out
 
     @torch.no_grad()
     def attribute_metrics(self, attributes, tokens=None, pool=None, thresh=0.75, ent_red_thresh=0.2):

@@ -17,8 +17,13 @@ Reconstruction quality is scored as recon_metrics.py scores it: SSIM (calculate_
 window of create_window) and MSE of decoded images against their inputs, one fused fp64 kernel
 (csrc/recon.hip) -- the section after TAD.  LPIPS is not computed.
 
-Out of scope: beta-VAE and DCI (they train sklearn classifiers) and the per-token PCA eval_func
-applies to 3-D token arrays -- the scalar codes are scored, as the reference does when it has them.
+DCI (evaluation/metrics/dci.py) fits one gradient-boosted classifier per factor: sklearn's default
+GradientBoostingClassifier, 100 stages of depth-3 trees, one tree per class.  Those are fitted on the
+device (csrc/gbt.hip) from the rows this file samples; the labels, the class prior and the entropies
+of the (D, K) importance matrix are host arithmetic -- the section after MIG.
+
+Out of scope: beta-VAE (it trains a logistic regression) and the per-token PCA eval_func applies to
+3-D token arrays -- the scalar codes are scored, as the reference does when it has them.
 """
 from __future__ import annotations
 
@@ -216,6 +221,121 @@ def mig_score(codes, grid, seed=0, num_train=10000, num_bins=NUM_BINS, edge_f64=
     ops.mig_hist(codes, _up(idx, dev), _up(fac, dev), grid.factor_sizes, edges, counts, edge_f64=edge_f64)
     ops.mig_finalize(counts, grid.factor_sizes, idx.shape[0], mi, h, score)
     return {"discrete_mig": float(score.item())}
+
+
+# ------------------------------------------------------------------ DCI
+DCI_MAX_TRAIN = 16384   # sums of 2^32-scaled gradients over the training rows stay in int64 (csrc/gbt.hip)
+DCI_MAX_CLASSES = 256
+DCI_KEYS = ("informativeness_train", "informativeness_test", "disentanglement", "completeness")
+
+
+def sample_dci(grid, random_state, num_train, num_test):
+    """(train_idx, train_factors, test_idx, test_factors): compute_dci's two calls of
+    generate_batch_factor_code on one random state, the training rows first (see sample_mig)."""
+    return sample_mig(grid, random_state, num_train) + sample_mig(grid, random_state, num_test)
+
+
+def dci_labels(y_train, y_test):
+    """(C, train labels, test labels) of one factor: the classes are the distinct values of the
+    training sample, numbered 0..C-1 in ascending order; a test value outside them becomes -1 and is
+    counted as wrong.  ValueError when C is 1 (sklearn refuses a single class) or above 256."""
+    values = np.unique(y_train)
+    c = int(values.size)
+    if c < 2:
+        raise ValueError("a factor takes one value in the training sample: the classifier needs at least 2 classes")
+    if c > DCI_MAX_CLASSES:
+        raise ValueError(f"a factor takes {c} values in the training sample: the tree kernels take C <= "
+                         f"{DCI_MAX_CLASSES} classes")
+    pos = np.minimum(np.searchsorted(values, y_test), c - 1)
+    test = np.where(values[pos] == y_test, pos, -1)
+    return c, np.searchsorted(values, y_train).astype(np.int32), test.astype(np.int32)
+
+
+def dci_init_raw(labels, classes):
+    """fp64 (T,): the raw predictions sklearn starts from, those of the class frequencies clipped to
+    [eps32, 1 - eps32]: log(p1 / (1 - p1)) for two classes, log(p) - mean(log(p)) otherwise."""
+    eps = float(np.finfo(np.float32).eps)
+    prior = np.clip(np.bincount(labels, minlength=classes) / float(len(labels)), eps, 1 - eps)
+    if classes == 2:
+        return np.array([np.log(prior[1] / (1 - prior[1]))])
+    lp = np.log(prior)
+    return lp - np.mean(lp)
+
+
+def _entropy(pk, base):
+    """scipy.stats.entropy(pk, base=base) along axis 0; restated (normalise, then -sum p log p /
+    log base) where scipy is absent."""
+    try:
+        from scipy.stats import entropy
+    except ImportError:
+        pk = pk / np.sum(pk, axis=0, keepdims=True)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return -np.sum(np.where(pk > 0, pk * np.log(pk), 0.0), axis=0) / np.log(base)
+    return entropy(pk, base=base)
+
+
+def dci_from_importance(importance_matrix):
+    """(disentanglement, completeness) of a (D, K) importance matrix, dci.py:105-135: one minus the
+    entropy (base K) of every code's row, weighted by the code's share of the total importance, and
+    one minus the entropy (base D) of every factor's column, weighted by the factor's share; an
+    all-zero matrix is weighted uniformly."""
+    im = np.asarray(importance_matrix, np.float64)
+    per_code = 1. - _entropy(im.T + 1e-11, im.shape[1])
+    per_factor = 1. - _entropy(im + 1e-11, im.shape[0])
+    w = np.ones_like(im) if im.sum() == 0. else im
+    dis = np.sum(per_code * (w.sum(axis=1) / w.sum()))
+    com = np.sum(per_factor * (w.sum(axis=0) / w.sum()))
+    return float(dis), float(com)
+
+
+def _check_dci(num_train, num_test, n_estimators):
+    if not 2 <= num_train <= DCI_MAX_TRAIN:
+        raise ValueError(f"num_train={num_train}: the tree kernels take 2..{DCI_MAX_TRAIN} training rows")
+    if num_test < 1:
+        raise ValueError(f"num_test={num_test}: at least one test row")
+    if n_estimators < 1:
+        raise ValueError(f"n_estimators={n_estimators}: at least one stage")
+
+
+def dci_score(codes, grid, seed=0, num_train=10000, num_test=5000, n_estimators=100, learning_rate=0.1, tie_seed=0):
+    """compute_dci of the reference with eval_func's sizes as defaults.  Returns
+    {"informativeness_train", "informativeness_test", "disentanglement", "completeness"} and
+    "importance_matrix", a (D, K) float64 numpy array.  The reference builds its classifiers unseeded,
+    so its scores vary from run to run with the order in which sklearn visits tied features; here
+    the ties are ranked by a hash of (tie_seed, stage, tree, node, feature) and a call repeats."""
+    _check_codes(codes, grid)
+    _check_dci(num_train, num_test, n_estimators)
+    idx_tr, f_tr, idx_te, f_te = sample_dci(grid, np.random.RandomState(seed), num_train, num_test)
+    K = grid.num_factors
+    labels = [dci_labels(f_tr[k], f_te[k]) for k in range(K)]
+    import torch
+    from . import ops
+    codes = _device_codes(codes)
+    dev, D = codes.device, codes.shape[1]
+    x_tr = torch.empty(num_train, D, device=dev, dtype=torch.float32)
+    x_te = torch.empty(num_test, D, device=dev, dtype=torch.float32)
+    ops.gbt_gather(codes, _up(idx_tr, dev), x_tr)
+    ops.gbt_gather(codes, _up(idx_te, dev), x_te)
+    xs, order = torch.sort(x_tr.t().contiguous(), dim=1, stable=True)
+    order = order.to(torch.int32)
+    ws = torch.empty(max(ops.gbt_workspace_bytes(num_train, num_test, D, c) for c, _, _ in labels), device=dev,
+                     dtype=torch.uint8)
+    importance = torch.empty(K, D, device=dev, dtype=torch.float64)
+    correct = torch.empty(K, 2, device=dev, dtype=torch.int32)
+    pred_tr = torch.empty(num_train, device=dev, dtype=torch.int32)
+    pred_te = torch.empty(num_test, device=dev, dtype=torch.int32)
+    for k, (c, y_tr, y_te) in enumerate(labels):
+        t = 1 if c == 2 else c
+        raw_tr = torch.empty(num_train, t, device=dev, dtype=torch.float64)
+        raw_te = torch.empty(num_test, t, device=dev, dtype=torch.float64)
+        ops.gbt_fit(x_tr, xs, order, _up(y_tr, dev), x_te, _up(y_te, dev), c, _up(dci_init_raw(y_tr, c), dev), ws,
+                    raw_tr, raw_te, pred_tr, pred_te, correct[k], importance[k], n_estimators=n_estimators,
+                    learning_rate=learning_rate, tie_seed=tie_seed)
+    im = np.abs(importance.cpu().numpy().T)
+    acc = correct.cpu().numpy().astype(np.float64) / np.array([num_train, num_test], np.float64)
+    dis, com = dci_from_importance(im)
+    return {"informativeness_train": float(np.mean(acc[:, 0])), "informativeness_test": float(np.mean(acc[:, 1])),
+            "disentanglement": dis, "completeness": com, "importance_matrix": im}
 
 
 # ------------------------------------------------------------------ TAD (CelebA attributes)

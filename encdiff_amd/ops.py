@@ -1600,8 +1600,69 @@ def mig_finalize(counts, factor_sizes, m, mi, h, score):
           "encdiff_mig_finalize")
 
 
+# ------------------------------------------------------------------ boosted trees for DCI
+GBT_MAX_TRAIN, GBT_MAX_CLASSES, GBT_NODES = 16384, 256, 15
+
+
+def gbt_gather(codes, idx, out):
+    """out fp32 [n][D] = codes[idx] (encdiff_gbt_gather)."""
+    N, D = _codes(codes).shape
+    n = idx.numel()
+    _dev(idx, torch.int32, (n,), "idx"), _dev(out, F32, (n, D), "out")
+    check(lib.encdiff_gbt_gather(_p(codes), N, D, _p(idx), n, _p(out), _s()), "encdiff_gbt_gather")
+
+
+def gbt_workspace_bytes(n_train, n_test, dims, classes):
+    """Bytes of gbt_fit's workspace for these sizes (encdiff_gbt_workspace)."""
+    b = C.c_longlong(0)
+    check(lib.encdiff_gbt_workspace(int(n_train), int(n_test), int(dims), int(classes), C.byref(b)),
+          "encdiff_gbt_workspace")
+    return int(b.value)
+
+
+def gbt_fit(x_train, x_sorted, order, y_train, x_test, y_test, classes, init_raw, workspace, raw_train, raw_test,
+            pred_train, pred_test, correct, importance, n_estimators=100, learning_rate=0.1, tie_seed=0,
+            trees_used=None, nodes=None):
+    """sklearn's default GradientBoostingClassifier of one factor (encdiff_gbt_fit): x_train fp32
+    [N][D], x_sorted fp32 / order int32 [D][N] (its columns sorted, stable), y_train int32 [N] in
+    0..classes-1, x_test fp32 [M][D], y_test int32 [M] (-1: no such class), init_raw fp64 [T], T = 1
+    for two classes and classes otherwise; workspace uint8 of gbt_workspace_bytes.  Outputs:
+    raw_train fp64 [N][T], raw_test fp64 [M][T], pred_train int32 [N], pred_test int32 [M], correct
+    int32 [2], importance fp64 [D]; optional trees_used int32 [1] and nodes = (feature int32,
+    threshold fp32, count int32, value fp64), each [n_estimators][T][15]."""
+    N, D = x_train.shape
+    M, T = x_test.shape[0], 1 if classes == 2 else classes
+    _dev(x_train, F32, (N, D), "x_train"), _dev(x_sorted, F32, (D, N), "x_sorted")
+    _dev(order, torch.int32, (D, N), "order"), _dev(y_train, torch.int32, (N,), "y_train")
+    _dev(x_test, F32, (M, D), "x_test"), _dev(y_test, torch.int32, (M,), "y_test")
+    _dev(init_raw, torch.float64, (T,), "init_raw")
+    _dev(raw_train, torch.float64, (N, T), "raw_train"), _dev(raw_test, torch.float64, (M, T), "raw_test")
+    _dev(pred_train, torch.int32, (N,), "pred_train"), _dev(pred_test, torch.int32, (M,), "pred_test")
+    _dev(correct, torch.int32, (2,), "correct"), _dev(importance, torch.float64, (D,), "importance")
+    need = gbt_workspace_bytes(N, M, D, classes)
+    assert workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous() and \
+        workspace.numel() >= need, f"workspace: {need} contiguous uint8 bytes on the device expected"
+    if trees_used is not None:
+        _dev(trees_used, torch.int32, (1,), "trees_used")
+    dbg = [None] * 4
+    if nodes is not None:
+        dbg = list(nodes)
+        for t, dt, what in zip(dbg, (torch.int32, F32, torch.int32, torch.float64),
+                               ("feature", "threshold", "count", "value")):
+            _dev(t, dt, (int(n_estimators), T, GBT_NODES), "nodes." + what)
+    a = L.GbtArgs(n_train=N, n_test=M, dims=D, classes=int(classes), n_estimators=int(n_estimators),
+                  learning_rate=float(learning_rate), tie_seed=int(tie_seed) & (2 ** 64 - 1),
+                  x_train=_p(x_train), x_sorted=_p(x_sorted), order=_p(order), y_train=_p(y_train),
+                  x_test=_p(x_test), y_test=_p(y_test), init_raw=_p(init_raw), workspace=_p(workspace),
+                  raw_train=_p(raw_train), raw_test=_p(raw_test), pred_train=_p(pred_train),
+                  pred_test=_p(pred_test), correct=_p(correct), importance=_p(importance),
+                  trees_used=_p(trees_used), dbg_feature=_p(dbg[0]), dbg_threshold=_p(dbg[1]),
+                  dbg_count=_p(dbg[2]), dbg_value=_p(dbg[3]))
+    check(lib.encdiff_gbt_fit(C.byref(a), _s()), "encdiff_gbt_fit")
+
+
 # ------------------------------------------------------------------ TAD (CelebA attribute metric)
-TAD_THRESHOLDS, TAD_MAX_ATTRS, TAD_COL_TILE, TAD_ROW_STEP = 11, 64, 32, 512
+TAD_THRESHOLDS,TAD_MAX_ATTRS, TAD_COL_TILE, TAD_ROW_STEP = 11, 64, 32, 512
 
 
 def _tad_z(z):

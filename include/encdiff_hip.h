@@ -1134,6 +1134,59 @@ int encdiff_ssim_mse(const EncdiffReconArgs* args, void* stream);
  * per tile of a plane. */
 int encdiff_ssim_mse_workspace(const EncdiffReconArgs* args, long long* bytes);
 
+/* ---------------------------------------------------------------- boosted trees for DCI
+ * The classifier of evaluation/metrics/dci.py compute_importance_gbt for ONE factor: sklearn's
+ * GradientBoostingClassifier with its defaults (log loss, friedman_mse, best splitter, max_depth 3,
+ * subsample 1), fitted on the device (csrc/gbt.hip; the algorithm is restated in numpy in
+ * tests/gbt_restate.py and described in DESIGN.md §1 "DCI").  T = classes trees per stage, 1 for two
+ * classes (the column of class 1).  Trees are grown on llrint(gradient * 2^32) as int64, so split
+ * statistics are exact integers; features whose best cuts tie are ranked by splitmix64(tie_seed,
+ * stage, tree, node, feature).  fp64 sums run in a fixed order without floating-point atomics: a
+ * second launch gives the same bits.  Nothing is allocated or read back; indices are clamped.
+ * Nodes carry heap ids 1..15 (children of i: 2 i, 2 i + 1); node tables are indexed by id - 1.
+ * Refusals, nothing is launched: a required pointer NULL, or some but not all dbg_ pointers set:
+ * ENCDIFF_ERR_ARG; 2 <= n_train <= 16384, 1 <= n_test < 2^24, 1 <= dims <= 64,
+ * 2 <= classes <= 256, 1 <= n_estimators <= 100000 otherwise: ENCDIFF_ERR_SHAPE. */
+#define ENCDIFF_GBT_MAX_TRAIN 16384
+#define ENCDIFF_GBT_MAX_CLASSES 256
+#define ENCDIFF_GBT_NODES 15
+
+typedef struct {
+  int n_train, n_test, dims, classes;
+  int n_estimators, pad_;
+  double learning_rate;
+  unsigned long long tie_seed;
+  const float* x_train;   /* fp32 [n_train][dims] */
+  const float* x_sorted;  /* fp32 [dims][n_train]: every column of x_train in ascending order */
+  const int* order;       /* int32 [dims][n_train]: the stable permutation that sorts the column */
+  const int* y_train;     /* int32 [n_train], class index 0..classes-1 */
+  const float* x_test;    /* fp32 [n_test][dims] */
+  const int* y_test;      /* int32 [n_test], class index, or -1: a label the training rows lack */
+  const double* init_raw; /* fp64 [T]: the raw predictions of the class prior */
+  void* workspace;        /* encdiff_gbt_workspace bytes, 8-byte aligned; written before it is read */
+  double* raw_train;      /* out fp64 [n_train][T] */
+  double* raw_test;       /* out fp64 [n_test][T] */
+  int* pred_train;        /* out int32 [n_train]: argmax (first maximum); raw >= 0 for two classes */
+  int* pred_test;         /* out int32 [n_test] */
+  int* correct;           /* out int32 [2]: rows predicted right, training and test */
+  double* importance;     /* out fp64 [dims]: feature_importances_ (zeros when no tree has a split) */
+  int* trees_used;        /* out int32 [1], optional: trees with at least one split */
+  /* optional node tables [n_estimators][T][15], all four or none: feature (-1 leaf, -2 no node),
+   * threshold (rows with x <= threshold go left), rows of the node, leaf value */
+  int* dbg_feature;
+  float* dbg_threshold;
+  int* dbg_count;
+  double* dbg_value;
+} EncdiffGbtArgs;
+
+/* out fp32 [n][dims] = codes[idx[i]] (row indices clamped to [0, n_rows)). */
+int encdiff_gbt_gather(const float* codes, int n_rows, int dims, const int* idx, int n, float* out, void* stream);
+
+/* bytes: the size of EncdiffGbtArgs.workspace for these sizes. */
+int encdiff_gbt_workspace(int n_train, int n_test, int dims, int classes, long long* bytes);
+
+int encdiff_gbt_fit(const EncdiffGbtArgs* args, void* stream);
+
 /* Library/device information (for tests): returns the number of exported kernels. */
 int encdiff_version(void);
 
