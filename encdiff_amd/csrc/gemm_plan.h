@@ -99,15 +99,23 @@ hipError_t launch_t(const EncdiffGemmArgs& p, const GemmAux& aux, hipStream_t s)
 
 // GroupNorm-in-staging forward conv (EncdiffGemmArgs.agn_*): 64x64 tiles, 2-deep ring, the
 // per-(image, channel) coefficient table behind the ring in dynamic LDS
-hipError_t launch_agn(const EncdiffGemmArgs& p, const GemmAux& aux, hipStream_t s) {
+constexpr size_t AGN_LDS_MAX = 156 * 1024;
+
+// dynamic LDS of the AGN kernel: prepare() refuses a problem whose table does not fit, launch_agn
+// allocates the same figure
+size_t agn_lds_bytes(const EncdiffGemmArgs& p) {
   using G = Gemm<64, 64, A_IM2COL_GN, B_ROWK, 2, BK>;
   const int hw = p.conv.h * p.conv.w;
   const int nimg = (63 / hw + 2) < p.conv.batch ? 63 / hw + 2 : p.conv.batch;  // images one 64-row tile reads
-  const size_t lds = (size_t)G::LDS_BYTES + (size_t)nimg * p.conv.cin * 8;
+  return (size_t)G::LDS_BYTES + (size_t)nimg * p.conv.cin * 8;
+}
+
+hipError_t launch_agn(const EncdiffGemmArgs& p, const GemmAux& aux, hipStream_t s) {
+  const size_t lds = agn_lds_bytes(p);
   static const hipError_t attr_ok = hipFuncSetAttribute((const void*)gemm_kernel<64, 64, A_IM2COL_GN, B_ROWK, 2, BK>,
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)AGN_LDS_MAX);
   if (attr_ok != hipSuccess) return attr_ok;
-  if (lds > 156 * 1024) return hipErrorInvalidValue;
+  if (lds > AGN_LDS_MAX) return hipErrorInvalidValue;  // prepare() refused it already
   dim3 grid((p.M + 63) / 64, (p.N + 63) / 64, p.split_k);
   hipLaunchKernelGGL((gemm_kernel<64, 64, A_IM2COL_GN, B_ROWK, 2, BK>), grid, dim3(256), lds, s, p, aux);
   return hipGetLastError();
@@ -356,10 +364,13 @@ int prepare(const EncdiffGemmArgs* pa, GemmPlan& g) {
     if (p.c_mode != ENCDIFF_OUT_BF16 || p.split_k != 1 || !p.tile || p.N > bn || p.N % 8 || p.ld_ln_y % 8 ||
         !p.ln_gamma || !p.ln_beta || !p.ln_stats)
       return ENCDIFF_ERR_ARG;
+    if ((uintptr_t)p.ln_y & 15) return ENCDIFF_ERR_ARG;  // written in 16-byte vectors on every path
   }
   if (p.c_mode == ENCDIFF_OUT_BF16_GEGLU || p.c_mode == ENCDIFF_OUT_BF16_GEGLU_BWD) {
     const bool fwd = p.c_mode == ENCDIFF_OUT_BF16_GEGLU;
     if (!p.aux || p.resid || p.split_k != 1 || p.N % 8 || p.ldc % 8 || p.ld_aux % 8) return ENCDIFF_ERR_ARG;
+    // both epilogues read / write aux and C in 16-byte vectors only (no scalar form)
+    if (((uintptr_t)p.aux & 15) || ((uintptr_t)p.c & 15)) return ENCDIFF_ERR_ARG;
     if (fwd && (p.a_mode != ENCDIFF_OPA_ROWK || p.b_mode != ENCDIFF_OPB_ROWK || p.N % 128)) return ENCDIFF_ERR_ARG;
   }
   if (p.agn_gamma) {  // GroupNorm in the A staging: forward 3x3 conv, 64x64 tiles
@@ -371,6 +382,8 @@ int prepare(const EncdiffGemmArgs* pa, GemmPlan& g) {
     if (p.conv.cin % 32 || p.conv.cin > 1024 || p.K != 9 * p.conv.cin ||
         (long)p.M != (long)p.conv.batch * p.conv.h * p.conv.w)
       return ENCDIFF_ERR_SHAPE;
+    // the coefficient table of the images one tile reads sits behind the ring (M > 0: h w > 0)
+    if (agn_lds_bytes(p) > AGN_LDS_MAX) return ENCDIFF_ERR_SHAPE;
     if (p.tile != 0 && p.tile != 4) return ENCDIFF_ERR_UNSUPPORTED;
     p.tile = 4;
   }

@@ -141,7 +141,8 @@ typedef struct EncdiffGemmArgs {
                                 (+ split_k*M when bias_grad is set: per-split bias-gradient slabs);
                                 each split writes its own [M][N] slab, a finalize pass sums the
                                 slabs in order (reproducible) and applies alpha/bias/resid    */
-  void* aux; long ld_aux;    /* GEGLU c_modes: y output (BF16_GEGLU) / f input (BF16_GEGLU_BWD)  */
+  void* aux; long ld_aux;    /* GEGLU c_modes: y output (BF16_GEGLU) / f input (BF16_GEGLU_BWD); aux and
+                                c 16-byte aligned, ld_aux % 8 == 0 and ldc % 8 == 0 (vector access only) */
   float* gn_stats; long ld_gn_stats;  /* optional, OUT_BF16 with split_k 1 and M % 64 == 0: per
                                 64-row segment s and column n, the sum and sum of squares of the
                                 bf16 outputs at gn_stats[(2s)*ld + n] and [(2s+1)*ld + n] -- the
@@ -149,7 +150,8 @@ typedef struct EncdiffGemmArgs {
                                 encdiff_groupnorm_fwd needs no reduction pass (in_stats)       */
   const float* ln_gamma;     /* optional LayerNorm of the produced rows (attention.py norm1/2/3): */
   const float* ln_beta;      /*   OUT_BF16, split_k 1, the tile spans all N columns (N <= 128);   */
-  void* ln_y; long ld_ln_y;  /*   ln_y = LN(C) bf16 from the stored bf16 C, two-pass fp32 stats,   */
+  void* ln_y; long ld_ln_y;  /*   ln_y = LN(C) bf16 from the stored bf16 C, two-pass fp32 stats; ln_y
+                                  16-byte aligned and ld_ln_y % 8 == 0 (written in vectors);          */
   float* ln_stats;           /*   ln_stats [M][2] (mean, rstd) for the backward                  */
   float ln_eps;
   int pad3_;
@@ -163,7 +165,9 @@ typedef struct EncdiffGemmArgs {
      -- ResBlock in_layers / out_layers (openaimodel_enc.py:201-205, 225-232, 267-271; util.py:242-244)
      -- applied to each staged tile in LDS, so the normalised activation never goes to memory.  Every
      workgroup computes the statistics (fp32 sum / sum of squares per (image, group), 32 groups) of
-     the images its output rows read, from x itself: x must be complete (no deferred slabs).
+     the images its output rows read, from x itself: x must be complete (no deferred slabs).  The
+     per-(image, channel) coefficients of those images (min(63 / (h w) + 2, batch) of them, 8 bytes
+     each) must fit the LDS behind the ring, else ENCDIFF_ERR_SHAPE.
      Replaces the encdiff_groupnorm_fwd launch in front of the conv where nothing saves its output
      (sampling / inference). */
   const float* agn_gamma;
@@ -172,8 +176,8 @@ typedef struct EncdiffGemmArgs {
   long ld_agn_film;
   float agn_eps;
   int agn_silu;
-  /* optional (lna_gamma != NULL), linear forwards OPA_ROWK x OPB_ROWK (bf16 / GEGLU output, tile 0
-     or 4, split 1, K <= 1024, K % 8 == 0): the A operand is LayerNorm(A) over its K channels --
+  /* optional (lna_gamma != NULL), linear forwards OPA_ROWK x OPB_ROWK (OUT_BF16 only, tile 0 or 4,
+     split 1, K <= 1024, K % 8 == 0, a 16-byte aligned): the A operand is LayerNorm(A) over its K channels --
      BasicTransformerBlock norm1 / norm2 / norm3 (attention.py:210-230) -- applied to each staged
      tile in LDS.  Every workgroup reduces the mean / rstd (fp32, one pass) of its rows from A in a
      prologue.  Replaces the encdiff_layernorm_fwd launch in front of the linear where nothing

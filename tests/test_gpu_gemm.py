@@ -35,9 +35,9 @@ largest |out - ref| measured on the MI355X (the whole file: 319 tests in about 5
     WGL 1.5e-4 / 9.4e-6; their bias gradients floor 1.0e-5, |out - ref| 2.6e-6
   fp32 GEMM (fp32.hip): floor 5.3e-5, |out - ref| 1.3e-5; bias gradients 8.0e-6 / 6.6e-6
 
-Out of scope: the non-linear fused stagings and epilogues (agn_*, lna_*, ln_y, OUT_BF16_GEGLU,
-OUT_BF16_GEGLU_BWD) need the norm restatements and a tolerance; they keep their tests in
-test_gpu_ops.py and are the natural follow-up.
+The non-linear fused stagings and epilogues (agn_*, lna_*, ln_y, OUT_BF16_GEGLU, OUT_BF16_GEGLU_BWD)
+need the norm restatements and derived bounds: tests/test_gpu_gemm_fused.py holds them per element,
+against tests/gemm_fused_restate.py.
 
 Kernel branch -> test
   gemm_tile ring: tiles 1-10 x the six operand-mode pairs of launch_one, ragged M and N,
