@@ -295,6 +295,13 @@ _PROTOS = {
     "encdiff_gbt_gather": [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp],
     "encdiff_gbt_workspace": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong)],
     "encdiff_gbt_fit": [C.POINTER(GbtArgs), vp],
+    "encdiff_beta_features": [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp],
+    "encdiff_logreg_workspace": [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong)],
+    "encdiff_logreg_fit": [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp],
+    "encdiff_logreg_predict": [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp],
+    "encdiff_token_workspace": [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_longlong)],
+    "encdiff_token_moments": [vp, C.c_longlong, C.c_int, C.c_int, vp, vp, vp, vp],
+    "encdiff_token_project": [vp, C.c_longlong, C.c_int, C.c_int, vp, vp, vp, vp],
     "encdiff_version": [],
 }
 

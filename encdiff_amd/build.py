@@ -39,9 +39,10 @@ def _headers():
 # template instantiations (GroupNorm backward with / without slab input, the split-K combine
 # restated from gemm_finalize.h) must round identically, and "fast" fuses across statements
 # differently per instantiation (test_unet_gn_fin_bitwise); the boosted trees of DCI round every
-# product and sum on its own, as their numpy restatement does (tests/gbt_restate.py)
+# product and sum on its own, as their numpy restatement does (tests/gbt_restate.py), and so does
+# the logistic regression of the beta-VAE score (tests/logreg_restate.py)
 FILE_FLAGS = {"attn_mfma.hip": ["-fno-honor-nans", "-mno-amdgpu-ieee"], "norm.hip": ["-ffp-contract=on"],
-              "gbt.hip": ["-ffp-contract=off"]}
+              "gbt.hip": ["-ffp-contract=off"], "beta_vae.hip": ["-ffp-contract=off"]}
 
 
 def _compile(src: str, obj: str, verbose: bool):

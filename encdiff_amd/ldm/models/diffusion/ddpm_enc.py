@@ -968,28 +968,38 @@ class LatentDiffusion(DDPM):
         return codes, toks
 
     @torch.no_grad()
-    def validation_metrics(self, codes=None, pool=None, seed=0, dci=False):
-        """The FactorVAE score and MIG of eval_func (main_val.py:74-94) on the device, under its
-        keys: {"factor_VAE": {train_accuracy, eval_accuracy, num_active_dims}, "MIG":
-        {discrete_mig}}.  codes: (N, latent_unit) scalar codes in dataset order (device tensor or
-        numpy), or pool: the validation image pool, encoded with encode_dataset.  The factor grid is
-        FactorGrid.named(self.eval_name).  dci=True adds "dci": {informativeness_train,
+    def validation_metrics(self, codes=None, pool=None, seed=0, dci=False, beta_vae=False, tokens=None):
+        """The scores of eval_func (main_val.py:74-94) on the device, under its keys: {"factor_VAE":
+        {train_accuracy, eval_accuracy, num_active_dims}, "MIG": {discrete_mig}}.  Exactly one of:
+        codes: (N, latent_unit) scalar codes in dataset order (device tensor or numpy); tokens: (N,
+        latent_unit, context_dim) concept tokens, reduced to one column per unit with
+        metrics.token_pca as eval_func reduces 3-D arrays, then scored like codes; pool: the
+        validation image pool, encoded with encode_dataset, whose scalar codes are scored.  The factor
+        grid is FactorGrid.named(self.eval_name).  dci=True adds "dci": {informativeness_train,
         informativeness_test, disentanglement, completeness} (metrics.dci_score: boosted trees fitted
-        on the device, 100 stages per factor).  beta-VAE is not computed."""
+        on the device, 100 stages per factor).  beta_vae=True adds "beta_VAE": {train_accuracy,
+        eval_accuracy} (metrics.beta_vae_score: the logistic regression fitted on the device)."""
         from encdiff_amd import metrics
-        if (codes is None) == (pool is None):
-            raise ValueError("validation_metrics takes either codes or pool")
+        if (codes is not None) + (pool is not None) + (tokens is not None) != 1:
+            raise ValueError("validation_metrics takes either codes or pool, or tokens: exactly one of the three")
         grid = metrics.FactorGrid.named(self.eval_name)
         if pool is not None:
             n = (pool.images if hasattr(pool, "images") else pool).shape[0]
             if n != grid.size:
                 raise ValueError(f"{n} images but the {self.eval_name} factor grid has {grid.size} observations")
             codes = self.encode_dataset(pool)[0]
+        if tokens is not None:
+            if tokens.shape[0] != grid.size:
+                raise ValueError(f"{tokens.shape[0]} token rows but the {self.eval_name} factor grid has {grid.size} "
+                                 f"observations")
+            codes = metrics.token_pca(tokens)[0]
         out = {"factor_VAE": metrics.factor_vae_score(codes, grid, seed=seed),
                "MIG": metrics.mig_score(codes, grid, seed=seed)}
         if dci:
             res = metrics.dci_score(codes, grid, seed=seed)
             out["dci"] = {k: res[k] for k in metrics.DCI_KEYS}
+        if beta_vae:
+            out["beta_VAE"] = metrics.beta_vae_score(codes, grid, seed=seed)
         return out
 
     @torch.no_grad()

@@ -22,8 +22,14 @@ GradientBoostingClassifier, 100 stages of depth-3 trees, one tree per class.  Th
 device (csrc/gbt.hip) from the rows this file samples; the labels, the class prior and the entropies
 of the (D, K) importance matrix are host arithmetic -- the section after MIG.
 
-Out of scope: beta-VAE (it trains a logistic regression) and the per-token PCA eval_func applies to
-3-D token arrays -- the scalar codes are scored, as the reference does when it has them.
+beta-VAE (evaluation/metrics/beta_vae.py) trains sklearn's default LogisticRegression on the mean
+|code difference| of row pairs that share one factor.  The feature table, the whole L-BFGS run (one
+launch of one workgroup) and the predictions are device work (csrc/beta_vae.hip); only the two
+accuracies and the fit's counters come back -- the section after DCI.
+
+eval_func reduces a 3-D token array (N, units, dim) to one column per unit with PCA(n_components=1).
+token_pca does that: moments and projection stream the tokens on the device (csrc/token_pca.hip),
+the units' dim x dim eigenproblems are host work -- the last section.
 """
 from __future__ import annotations
 
@@ -129,8 +135,8 @@ def accuracy_from_votes(train_votes, eval_votes):
 # ------------------------------------------------------------------ checks (host, before any launch)
 def _check_codes(codes, grid):
     if codes.ndim != 2:
-        raise ValueError(f"codes must be (N, D) scalar codes, got shape {tuple(codes.shape)}; the PCA of "
-                         f"(N, units, dim) tokens is out of scope")
+        raise ValueError(f"codes must be (N, D) scalar codes, got shape {tuple(codes.shape)}; reduce "
+                         f"(N, units, dim) tokens with metrics.token_pca, or pass tokens= to validation_metrics")
     n, d = codes.shape
     if n != grid.size:
         raise ValueError(f"{n} code rows but the factor grid {grid.factor_sizes} has {grid.size} observations")
@@ -336,6 +342,132 @@ def dci_score(codes, grid, seed=0, num_train=10000, num_test=5000, n_estimators=
     dis, com = dci_from_importance(im)
     return {"informativeness_train": float(np.mean(acc[:, 0])), "informativeness_test": float(np.mean(acc[:, 1])),
             "disentanglement": dis, "completeness": com, "importance_matrix": im}
+
+
+# ------------------------------------------------------------------ beta-VAE
+def sample_beta_vae(grid, random_state, batch_size, num_points):
+    """idx1, idx2 int32 (P, batch) and labels int32 (P,): per point randint(num_factors), then
+    sample_factors(batch_size) twice, the chosen column of the second set to the first's
+    (beta_vae.py _generate_training_sample; every factor is latent, so the observations draw nothing)."""
+    idx1 = np.empty((num_points, batch_size), dtype=np.int32)
+    idx2 = np.empty((num_points, batch_size), dtype=np.int32)
+    labels = np.empty(num_points, dtype=np.int32)
+    for p in range(num_points):
+        k = random_state.randint(grid.num_factors)
+        f1 = grid.sample_factors(batch_size, random_state)
+        f2 = grid.sample_factors(batch_size, random_state)
+        f2[:, k] = f1[:, k]
+        idx1[p], idx2[p], labels[p] = grid.index(f1), grid.index(f2), k
+    return idx1, idx2, labels
+
+
+def _check_beta_vae(grid, batch_size, num_train, num_eval, C, max_iter, tol):
+    if grid.num_factors < 3:
+        raise ValueError(f"{grid.num_factors} factors: with two classes sklearn fits a binary objective, which the "
+                         f"logistic-regression kernel does not (at least 3 factors)")
+    if grid.num_factors > MAX_FACTORS:
+        raise ValueError(f"{grid.num_factors} factors: the logistic-regression kernel takes at most {MAX_FACTORS}")
+    if not 2 <= batch_size <= 64:
+        raise ValueError(f"batch_size={batch_size}: the feature kernel takes 2..64 row pairs per point")
+    if not 1 <= num_train <= 2 ** 20 or not 1 <= num_eval < 2 ** 24:
+        raise ValueError(f"num_train={num_train}, num_eval={num_eval}: 1..2^20 training and 1..2^24-1 evaluation points")
+    if not 1 <= max_iter <= 1000 or not C > 0 or not tol >= 0:
+        raise ValueError(f"C={C}, max_iter={max_iter}, tol={tol}: C > 0, 1 <= max_iter <= 1000, tol >= 0")
+
+
+def beta_vae_score(codes, grid, seed=0, batch_size=64, num_train=10000, num_eval=5000, C=1.0, max_iter=100, tol=1e-4,
+                   return_fit=False):
+    """compute_beta_vae_sklearn of the reference with eval_func's bindings as defaults: sklearn's
+    default LogisticRegression (multinomial, L2 with C, L-BFGS from zero, max_iter, tol) on the
+    features mean_b |codes[idx1] - codes[idx2]|.  Returns {"train_accuracy", "eval_accuracy"}; with
+    return_fit also "coef" (K, D), "intercept" (K,), "n_iter", "n_fev", "status", "loss".  ValueError
+    before any launch: fewer than 3 or more than 16 factors, a factor that never occurs as a training
+    label (sklearn would fit fewer classes), D outside 1..64.  RuntimeError when a line search of the
+    fit ends without meeting its test (status 3)."""
+    _check_codes(codes, grid)
+    _check_beta_vae(grid, batch_size, num_train, num_eval, C, max_iter, tol)
+    rs = np.random.RandomState(seed)
+    train = sample_beta_vae(grid, rs, batch_size, num_train)
+    ev = sample_beta_vae(grid, rs, batch_size, num_eval)
+    K = grid.num_factors
+    missing = np.nonzero(np.bincount(train[2], minlength=K) == 0)[0]
+    if missing.size:
+        raise ValueError(f"factor {int(missing[0])} never occurs as a label among the {num_train} training points: "
+                         f"sklearn would fit {K - missing.size} classes")
+    import torch
+    from . import ops
+    codes = _device_codes(codes)
+    dev, D = codes.device, codes.shape[1]
+    f64 = dict(device=dev, dtype=torch.float64)
+    coef, intercept, loss = torch.empty(K, D, **f64), torch.empty(K, **f64), torch.empty(1, **f64)
+    info = torch.empty(4, device=dev, dtype=torch.int32)
+    correct = torch.empty(2, 1, device=dev, dtype=torch.int32)
+    ws = torch.empty(ops.logreg_workspace_bytes(num_train, D, K), device=dev, dtype=torch.uint8)
+    for i, (idx1, idx2, labels) in enumerate((train, ev)):
+        x = torch.empty(idx1.shape[0], D, **f64)
+        labels = _up(labels, dev)
+        ops.beta_features(codes, _up(idx1, dev), _up(idx2, dev), x)
+        if i == 0:
+            ops.logreg_fit(x, labels, K, ws, coef, intercept, info, loss, C_reg=C, max_iter=max_iter, tol=tol)
+        ops.logreg_predict(x, labels, coef, intercept, correct[i])
+    n_iter, n_fev, status, _ = (int(v) for v in info.cpu().numpy())
+    if status == 3:
+        raise RuntimeError(f"the logistic regression's line search failed in iteration {n_iter} (after {n_fev} "
+                           f"evaluations): {ops.LOGREG_STATUS[3]}")
+    hits = correct.cpu().numpy().reshape(2)
+    out = {"train_accuracy": float(hits[0] / np.float64(num_train)), "eval_accuracy": float(hits[1] / np.float64(num_eval))}
+    if return_fit:
+        out.update(coef=coef.cpu().numpy(), intercept=intercept.cpu().numpy(), n_iter=n_iter, n_fev=n_fev,
+                   status=status, loss=float(loss.item()))
+    return out
+
+
+# ------------------------------------------------------------------ token PCA
+TOKEN_MAX = 64          # units and numbers per unit (csrc/token_pca.hip)
+
+
+def pca_sign(v):
+    """The component signed as sklearn >= 1.5 signs it (svd_flip(u_based_decision=False)): its entry
+    of largest magnitude, the first of equals, is positive."""
+    s = np.sign(v[np.argmax(np.abs(v))])
+    return v * (s if s != 0 else 1.0)
+
+
+def token_components(cov):
+    """(components (U, d), explained_variance (U,)) float64 from the units' covariances (U, d, d): the
+    eigenvector of the largest eigenvalue (np.linalg.eigh), signed by pca_sign."""
+    cov = np.asarray(cov, np.float64)
+    w, v = np.linalg.eigh(cov)
+    comps = np.stack([pca_sign(v[u, :, -1]) for u in range(cov.shape[0])])
+    return comps, w[:, -1].copy()
+
+
+def token_pca(tokens):
+    """PCA(n_components=1).fit_transform of every unit of tokens (N, U, d) (device tensor or numpy,
+    float32), as eval_func reduces 3-D token arrays: returns (codes (N, U) float32 device tensor,
+    components (U, d), mean (U, d), explained_variance (U,)), the last three float64 numpy."""
+    shape = tuple(tokens.shape)
+    if len(shape) != 3:
+        raise ValueError(f"tokens must be (N, units, dim), got shape {shape}")
+    n, u, d = shape
+    if n < 2:
+        raise ValueError(f"{n} token rows: the covariance (ddof = 1) needs at least 2")
+    if not (1 <= u <= TOKEN_MAX and 1 <= d <= TOKEN_MAX):
+        raise ValueError(f"{u} units of {d} numbers: the token kernels take 1..{TOKEN_MAX} of each")
+    import torch
+    from . import ops
+    tokens = _device_codes(tokens)
+    if tokens.data_ptr() % 16:  # a view at an odd offset: the kernels load 16 bytes at a time
+        tokens = tokens.clone()
+    dev = tokens.device
+    mean = torch.empty(u, d, device=dev, dtype=torch.float64)
+    cov = torch.empty(u, d, d, device=dev, dtype=torch.float64)
+    ws = torch.empty(ops.token_workspace_bytes(n, u, d), device=dev, dtype=torch.uint8)
+    ops.token_moments(tokens, ws, mean, cov)
+    comps, ev = token_components(cov.cpu().numpy())
+    codes = torch.empty(n, u, device=dev, dtype=torch.float32)
+    ops.token_project(tokens, mean, _up(comps, dev), codes)
+    return codes, comps, mean.cpu().numpy(), ev
 
 
 # ------------------------------------------------------------------ TAD (CelebA attributes)

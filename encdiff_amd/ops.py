@@ -1661,6 +1661,102 @@ def gbt_fit(x_train, x_sorted, order, y_train, x_test, y_test, classes, init_raw
     check(lib.encdiff_gbt_fit(C.byref(a), _s()), "encdiff_gbt_fit")
 
 
+# ------------------------------------------------------------------ beta-VAE score
+LOGREG_STATUS = ("converged: max |gradient| <= tol", "converged: relative reduction of the loss",
+                 "max_iter reached", "a line search ended without meeting its test")
+
+
+def beta_features(codes, idx1, idx2, out):
+    """out fp64 [P][D] = mean_b |codes[idx1[p][b]] - codes[idx2[p][b]]| in float32, sum order b =
+    0..B-1, then widened (encdiff_beta_features).  idx1, idx2 int32 [P][B], 2 <= B <= 64."""
+    N, D = _codes(codes).shape
+    assert idx1.dim() == 2
+    P, B = idx1.shape
+    _dev(idx1, torch.int32, (P, B), "idx1"), _dev(idx2, torch.int32, (P, B), "idx2")
+    _dev(out, torch.float64, (P, D), "out")
+    check(lib.encdiff_beta_features(_p(codes), N, D, _p(idx1), _p(idx2), P, B, _p(out), _s()), "encdiff_beta_features")
+
+
+def logreg_workspace_bytes(n, dims, classes):
+    """Bytes of logreg_fit's workspace (encdiff_logreg_workspace)."""
+    b = C.c_longlong(0)
+    check(lib.encdiff_logreg_workspace(int(n), int(dims), int(classes), C.byref(b)), "encdiff_logreg_workspace")
+    return int(b.value)
+
+
+def logreg_fit(x, y, classes, workspace, coef, intercept, info, loss, C_reg=1.0, max_iter=100, tol=1e-4):
+    """sklearn's default multinomial LogisticRegression in one launch (encdiff_logreg_fit): x fp64
+    [n][D], y int32 [n] in 0..classes-1, workspace uint8 of logreg_workspace_bytes.  Outputs: coef
+    fp64 [K][D], intercept fp64 [K], info int32 [4] (iterations, evaluations, status, most
+    evaluations of one line search; LOGREG_STATUS names the status), loss fp64 [1]."""
+    assert x.dim() == 2
+    n, D = x.shape
+    K = int(classes)
+    _dev(x, torch.float64, (n, D), "x"), _dev(y, torch.int32, (n,), "y")
+    _dev(coef, torch.float64, (K, D), "coef"), _dev(intercept, torch.float64, (K,), "intercept")
+    _dev(info, torch.int32, (4,), "info"), _dev(loss, torch.float64, (1,), "loss")
+    need = logreg_workspace_bytes(n, D, K)
+    assert workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous() and \
+        workspace.numel() >= need, f"workspace: {need} contiguous uint8 bytes on the device expected"
+    check(lib.encdiff_logreg_fit(_p(x), _p(y), n, D, K, float(C_reg), int(max_iter), float(tol), _p(workspace),
+                                 _p(coef), _p(intercept), _p(info), _p(loss), _s()), "encdiff_logreg_fit")
+
+
+def logreg_predict(x, labels, coef, intercept, correct, decisions=None, pred=None):
+    """correct int32 [1] = rows of x fp64 [P][D] whose first-maximum argmax of x coef^T + intercept
+    equals labels int32 [P]; optional decisions fp64 [P][K] and pred int32 [P] (encdiff_logreg_predict)."""
+    assert x.dim() == 2 and coef.dim() == 2
+    P, D = x.shape
+    K = coef.shape[0]
+    _dev(x, torch.float64, (P, D), "x"), _dev(labels, torch.int32, (P,), "labels")
+    _dev(coef, torch.float64, (K, D), "coef"), _dev(intercept, torch.float64, (K,), "intercept")
+    _dev(correct, torch.int32, (1,), "correct")
+    if decisions is not None:
+        _dev(decisions, torch.float64, (P, K), "decisions")
+    if pred is not None:
+        _dev(pred, torch.int32, (P,), "pred")
+    check(lib.encdiff_logreg_predict(_p(x), _p(labels), P, D, K, _p(coef), _p(intercept), _p(correct), _p(decisions),
+                                     _p(pred), _s()), "encdiff_logreg_predict")
+
+
+# ------------------------------------------------------------------ token PCA
+from .metrics import TOKEN_MAX  # noqa: E402  (64 units, 64 numbers per unit; metrics.py imports numpy alone)
+
+
+def _tokens(tokens):
+    assert tokens.dim() == 3 and 1 <= tokens.shape[1] <= TOKEN_MAX and 1 <= tokens.shape[2] <= TOKEN_MAX, \
+        f"tokens: (N, U, d) with U, d <= {TOKEN_MAX} expected, got {tuple(tokens.shape)}"
+    return _dev(tokens, F32, tokens.shape, "tokens")
+
+
+def token_workspace_bytes(n, units, dim):
+    """Bytes of token_moments' workspace (encdiff_token_workspace)."""
+    b = C.c_longlong(0)
+    check(lib.encdiff_token_workspace(int(n), int(units), int(dim), C.byref(b)), "encdiff_token_workspace")
+    return int(b.value)
+
+
+def token_moments(tokens, workspace, mean, cov):
+    """mean fp64 [U][d] and cov fp64 [U][d][d] (ddof = 1) of tokens fp32 [N][U][d], N >= 2
+    (encdiff_token_moments); workspace uint8 of token_workspace_bytes."""
+    N, U, d = _tokens(tokens).shape
+    _dev(mean, torch.float64, (U, d), "mean"), _dev(cov, torch.float64, (U, d, d), "cov")
+    need = token_workspace_bytes(N, U, d)
+    assert workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous() and \
+        workspace.numel() >= need, f"workspace: {need} contiguous uint8 bytes on the device expected"
+    check(lib.encdiff_token_moments(_p(tokens), N, U, d, _p(workspace), _p(mean), _p(cov), _s()),
+          "encdiff_token_moments")
+
+
+def token_project(tokens, mean, components, out):
+    """out fp32 [N][U] = sum_i (tokens - mean) * components in fp64, rounded (encdiff_token_project)."""
+    N, U, d = _tokens(tokens).shape
+    _dev(mean, torch.float64, (U, d), "mean"), _dev(components, torch.float64, (U, d), "components")
+    _dev(out, F32, (N, U), "out")
+    check(lib.encdiff_token_project(_p(tokens), N, U, d, _p(mean), _p(components), _p(out), _s()),
+          "encdiff_token_project")
+
+
 # ------------------------------------------------------------------ TAD (CelebA attribute metric)
 TAD_THRESHOLDS,TAD_MAX_ATTRS, TAD_COL_TILE, TAD_ROW_STEP = 11, 64, 32, 512
 

@@ -1191,6 +1191,65 @@ int encdiff_gbt_workspace(int n_train, int n_test, int dims, int classes, long l
 
 int encdiff_gbt_fit(const EncdiffGbtArgs* args, void* stream);
 
+/* ---------------------------------------------------------------- beta-VAE score
+ * evaluation/metrics/beta_vae.py on the device (csrc/beta_vae.hip; restated in numpy in
+ * tests/logreg_restate.py, described in DESIGN.md §1 "beta-VAE"): the feature table, sklearn's
+ * default multinomial LogisticRegression (L-BFGS as scipy's L-BFGS-B runs it without bounds) and
+ * the accuracy of its predictions.  Everything is device memory.  Sums run in a fixed order with no
+ * floating-point atomics: a second launch gives the same bits.  Nothing is allocated or read back.
+ * Refusals, nothing is launched: a required pointer NULL or a misaligned workspace:
+ * ENCDIFF_ERR_ARG; a size outside the stated limits: ENCDIFF_ERR_SHAPE. */
+#define ENCDIFF_LOGREG_MAX_ROWS (1 << 20)
+#define ENCDIFF_LOGREG_PAIRS 10
+
+/* out fp64 [points][dims]: out[p][d] = np.mean(np.abs(codes[idx1[p]] - codes[idx2[p]]), axis=0)[d] as
+ * numpy evaluates it on float32 rows: a float32 sum in the order b = 0..batch-1, one float32
+ * division by batch, widened.  idx1, idx2 int32 [points][batch], row indices clamped to [0, n_rows).
+ * 2 <= batch <= 64, 1 <= dims <= 64. */
+int encdiff_beta_features(const float* codes, int n_rows, int dims, const int* idx1, const int* idx2, int points,
+                          int batch, double* out, void* stream);
+
+/* bytes: the size of encdiff_logreg_fit's workspace: the (n, classes) residual and the ten (s, y)
+ * pairs, 8 (n classes + 20 classes (dims + 1)). */
+int encdiff_logreg_workspace(int n, int dims, int classes, long long* bytes);
+
+/* Minimises (1/n) sum_i [logsumexp(z_i) - z_i,y_i] + (1 / (2 C n)) |W|^2, z = x W^T + b, from W = 0,
+ * b = 0, in one launch of one workgroup.  x fp64 [n][dims], y int32 [n] in 0..classes-1 (clamped).
+ * Outputs: coef fp64 [classes][dims], intercept fp64 [classes], loss fp64 [1] (the last value), info
+ * int32 [4]: iterations, loss evaluations, status, the most evaluations one line search took.
+ * status 0: max |gradient| <= tol; 1: f_old - f <= 64 eps max(|f_old|, |f|, 1); 2: max_iter reached;
+ * 3: a line search ended without meeting its test (the point of its last evaluation is returned).
+ * 1 <= n <= 2^20, 1 <= dims <= 64, 3 <= classes <= 16, 1 <= max_iter <= 1000, C > 0, tol >= 0;
+ * workspace: encdiff_logreg_workspace bytes, 8-byte aligned, written before it is read. */
+int encdiff_logreg_fit(const double* x, const int* y, int n, int dims, int classes, double C, int max_iter,
+                       double tol, void* workspace, double* coef, double* intercept, int* info, double* loss,
+                       void* stream);
+
+/* correct int32 [1] (zeroed by the call) = #{p : argmax_k (x[p] . coef[k] + intercept[k]) == labels[p]},
+ * the first maximum as np.argmax takes it.  Optional outputs (NULL: not written): decisions fp64
+ * [points][classes] and pred int32 [points].  1 <= points < 2^24, 1 <= classes <= 16. */
+int encdiff_logreg_predict(const double* x, const int* labels, int points, int dims, int classes, const double* coef,
+                           const double* intercept, int* correct, double* decisions, int* pred, void* stream);
+
+/* ---------------------------------------------------------------- token PCA
+ * The moments and the projection of eval_func's PCA(n_components=1) over tokens fp32 [n][units][dim]
+ * (csrc/token_pca.hip), 16-byte aligned, 2 <= n < 2^31, units and dim in 1..64; the eigenvectors are
+ * host work (encdiff_amd/metrics.py token_pca).  fp64 sums in a fixed order, no floating-point
+ * atomics.  Refusals as above. */
+#define ENCDIFF_TOKEN_MAX 64
+
+/* bytes: the size of encdiff_token_moments' workspace (per-block partial sums). */
+int encdiff_token_workspace(long long n, int units, int dim, long long* bytes);
+
+/* mean fp64 [units][dim] and cov fp64 [units][dim][dim], the ddof = 1 covariance of every unit's rows,
+ * from one pass shifted by row 0. */
+int encdiff_token_moments(const float* tokens, long long n, int units, int dim, void* workspace, double* mean,
+                          double* cov, void* stream);
+
+/* out fp32 [n][units]: sum_i (tokens[n][u][i] - mean[u][i]) components[u][i] in fp64, rounded.  n >= 1. */
+int encdiff_token_project(const float* tokens, long long n, int units, int dim, const double* mean,
+                          const double* components, float* out, void* stream);
+
 /* Library/device information (for tests): returns the number of exported kernels. */
 int encdiff_version(void);
 
